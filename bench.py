@@ -9,6 +9,7 @@ sage_dgl_partition.py:train() makes the layer do per iteration.  The frontier of
 workload uses 409 600 = 2048 x 200 unique uniform ids, bag length 1, as DGL delivers them.
 
   python bench.py --gpus 1 --steps 50 --warmup 10
+  python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   (also writes the last timed step's outputs)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 is data parallel (weak scaling): every rank looks up its own batch, the flattened
@@ -297,7 +298,12 @@ def main():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the batch-2048 and METIS-like legs (keeps a rocprofv3 summary to the headline workload)")
     ap.add_argument("--path", default="auto", choices=["auto", "generic", "fast3"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "a fixed seeded sample of the rows of its forward output, and the TT cores after its update")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (`python bench.py --gpus N`): the ranks are fresh child processes, one per GPU, started
@@ -337,6 +343,9 @@ def main():
     dp = TTDataParallel(emb) if world > 1 else None
     if dp is not None:
         dp.broadcast_parameters(0)
+    # every step updates the cores and the pre-warm below runs for a wall-clock budget: the timed steps start again from
+    # these initial cores, so that what they compute depends on the arguments only
+    init_cores = [c.detach().clone() for c in emb.tt_cores]
     rng = np.random.default_rng(2 + rank)
     n_sets = 4  # rotate a few frontiers so that no step re-reads the previous step's ids
     id_sets = [torch.from_numpy(rng.choice(N_EMB, size=N, replace=False).astype(np.int64)).cuda()
@@ -349,6 +358,7 @@ def main():
         out.backward(d_out)
         if dp is not None:
             dp.step(overlap=True)   # the all-reduce runs under the next forward's grouping pass
+        return out
 
     def fence():
         if dp is not None:
@@ -381,12 +391,20 @@ def main():
     for i in range(args.warmup):
         step(i)
     fence()
+    with torch.no_grad():
+        for c, c0 in zip(emb.tt_cores, init_cores):
+            c.copy_(c0)
+    fence()
     ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     step_evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
+    last_out = None
     t0 = time.perf_counter()
     ev_a.record()
     for i in range(args.steps):
-        step(i)
+        if i == args.steps - 1:
+            last_out = step(i)
+        else:
+            step(i)
         step_evs[i].record()
     if dp is not None:
         dp.flush()              # the last step's update belongs to the timed region
@@ -395,6 +413,15 @@ def main():
     elapsed = time.perf_counter() - t0
     gpu_ms = ev_a.elapsed_time(ev_b)   # the same region on the GPU's clock (first launch .. last kernel's end)
     step_gpu_ms = [(ev_a if i == 0 else step_evs[i - 1]).elapsed_time(step_evs[i]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        # the whole forward output is N x D floats (164 MB at the default N): a fixed seeded sample of its rows
+        rows = np.sort(np.random.default_rng(0).choice(N, size=min(N, 65536), replace=False))
+        dump = {"forward_out_rows": last_out.detach()[torch.from_numpy(rows).cuda()]}
+        dump.update({f"tt_core{t}": c.detach() for t, c in enumerate(emb.tt_cores)})
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.float().cpu().numpy())
+    del last_out
     dist_info = None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else "cuda")

@@ -25,6 +25,9 @@ def _worker(rank, world, port, out_dir):
             sys.path.insert(0, p)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    # a CPU test on every machine: the module is built on the GPU whenever torch sees one, and `world` worker processes
+    # with the GPU open are more than a shared GPU allows -- the workers never initialise it (see also the barrier below)
+    torch.cuda.is_available = lambda: False
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from FBTT.tt_embeddings_ops import TTEmbeddingBag
     from ttemb_dist import TTDataParallel
@@ -55,7 +58,7 @@ def _worker(rank, world, port, out_dir):
     dp.flush()   # idempotent
     assert all(torch.equal(c.detach(), e) for c, e in zip(m.tt_cores, end2))
     torch.save({"start": start, "grads": grads, "end": end, "end2": end2}, os.path.join(out_dir, f"rank{rank}.pt"))
-    dist.barrier()
+    dist.monitored_barrier()   # (gloo's host-side barrier: dist.barrier() asks for the accelerator, which initialises it)
     dist.destroy_process_group()
 
 

@@ -257,7 +257,7 @@ def test_initialisers(dist):
     torch.manual_seed(0)
     n = 27000
     m = TTEmbeddingBag(n, 64, [8, 8], [30, 30, 30], [4, 4, 4], use_cache=False, weight_dist=dist)
-    cores = [c.detach().numpy() for c in m.tt_cores]
+    cores = [c.detach().cpu().numpy() for c in m.tt_cores]
     assert all(np.isfinite(c).all() for c in cores)
     if dist == "normal":
         for c in cores:
@@ -275,7 +275,7 @@ def test_initialisers(dist):
             assert np.abs(c).min() >= 2 * s * (1 - 1e-6)
     else:
         # the product table should look roughly uniform on (-1, 1) / sqrt(n): mean |x| ~ 0.5 / sqrt(n)
-        full = m.full_weight().detach().numpy()
+        full = m.full_weight().detach().cpu().numpy()
         assert np.isfinite(full).all() and 0.3 < np.abs(full).mean() * np.sqrt(n) < 0.7
 
 

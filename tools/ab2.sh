@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/ab2.sh "<kbench args A>" "<kbench args B>" ...  -- every lib/libttemb_*.so x every arg set
-cd $GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
+cd $R
 for args in "$@"; do
   for lib in falcon-ttdforgnns_amd/lib/libttemb_*.so; do
     echo -n "$(basename $lib .so | sed s/libttemb_//) [$args] : "

@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box): tools/ab_prof.sh <kernel-name-regex> [kbench args]  -- per-kernel averages per lib/libttemb_*.so
 pat=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 for lib in $R/falcon-ttdforgnns_amd/lib/libttemb_*.so; do
   tag=abp_$(basename $lib .so)
   rm -rf $R/gpurun_out/$tag

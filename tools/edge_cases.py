@@ -1,5 +1,6 @@
-import sys
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/falcon-ttdforgnns_amd')
+import os, sys
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0,ROOT); sys.path.insert(0,os.path.join(ROOT,'falcon-ttdforgnns_amd'))
 import numpy as np, torch
 from FBTT.tt_embeddings_ops import TTEmbeddingBag
 from oracle import tt_oracle as orc

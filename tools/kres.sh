@@ -1,7 +1,7 @@
 #!/bin/bash
 # prints registers / occupancy of the ttemb kernels in one .hip file (compile-only)
 f=${1:-ttemb_fast3.hip}; shift
-cd /root/repo/falcon-ttdforgnns_amd/csrc
+cd "$(dirname "$0")/../falcon-ttdforgnns_amd/csrc"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -I../../include "$@" -c $f -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c "
 import sys,re
 cur={}

@@ -3,9 +3,9 @@
 # One counter-only rocprofv3 pass (SQ_VALU_MFMA_BUSY_CYCLES, SQ_BUSY_CYCLES, GRBM_GUI_ACTIVE, SQ_WAVES) over
 # tools/kbench.py --iters 5, plus a kernel-trace pass for the durations; MFMA-pipe utilisation of a kernel =
 # MFMA busy cycles summed over the 1024 SIMDs / (duration x 2.4 GHz x 1024).
-out=$(cd $GRAFT_REPO_ROOT && realpath -m "$1")
+R=$(cd "$(dirname "$0")/.." && pwd)
+out=$(cd $R && realpath -m "$1")
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 rm -rf $R/gpurun_out/pmc_mfma $R/gpurun_out/pmc_mfma_t
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d $R/gpurun_out/pmc_mfma -- python3 $R/tools/kbench.py --iters 5 $TRAFFIC_KBENCH_ARGS > $R/gpurun_out/pmc_mfma.log 2>&1 || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/pmc_mfma_t -- python3 $R/tools/kbench.py --iters 5 $TRAFFIC_KBENCH_ARGS > $R/gpurun_out/pmc_mfma_t.log 2>&1 || exit 1

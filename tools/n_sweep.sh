@@ -1,6 +1,6 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 for n in 102400 204800 409600 819200; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/nsw_$n -- python3 $R/tools/kbench.py --iters 10 --n $n --what bwd > $R/gpurun_out/nsw_$n.log 2>&1
   python3 - <<PY

@@ -3,7 +3,7 @@
 # Counter-only rocprofv3 passes with SQ wave-state / instruction-mix counters over tools/kbench.py --iters 5;
 # prints per-kernel averages (tools/pmc_summary.py) into gpurun_out/<tag>.txt
 tag=$1; shift
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/$tag
 rm -rf $O; mkdir -p $O

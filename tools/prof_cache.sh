@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box): tools/prof_cache.sh <tag>  -> per-kernel averages of tools/cache_bench.py
 tag=${1:-prof_cache}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$tag -- python3 $R/tools/cache_bench.py > $R/gpurun_out/$tag.log 2>&1
 cat $R/gpurun_out/$tag.log | grep -v amdgpu.ids
 python3 - <<PY

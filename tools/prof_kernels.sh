@@ -1,8 +1,8 @@
 #!/bin/bash
 # usage (on the GPU box): tools/prof_kernels.sh <tag> [kbench args...]  -> prints per-kernel averages
 tag=$1; shift
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/$tag -- python3 $R/tools/kbench.py "$@" > $R/gpurun_out/$tag.log 2>&1
 python3 - <<PY
 import csv,glob

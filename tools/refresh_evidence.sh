@@ -4,7 +4,7 @@
 # the rocprofv3 --kernel-trace --stats summary of a short bench.py run, and the default bench.py line.
 # Everything lands in gpurun_out/<tag>/ (copy what should be judged into profiles/).
 tag=${1:-evidence}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/$tag
 mkdir -p $O
 bash $R/tools/traffic.sh profiles/r05_traffic.json > $O/traffic.log 2>&1 || exit 1

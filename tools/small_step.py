@@ -1,5 +1,5 @@
 import os, sys
-ROOT='/root/repo'
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "falcon-ttdforgnns_amd")): sys.path.insert(0,p)
 import numpy as np, torch
 from FBTT.tt_embeddings_ops import TTEmbeddingBag
