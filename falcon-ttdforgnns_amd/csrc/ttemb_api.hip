@@ -188,15 +188,15 @@ static bool use_fast3(const DevShape& s, int64_t nnz, int64_t B, bool have_offse
   if (!fast3_fits(s, nnz, B) && !(have_offsets && fast3_fits_in_pieces(s, nnz, B))) return false;
   return path == TTEMB_PATH_FAST3 || fast3_pays(s, nnz);
 }
-// the fused optimiser step rides in the grouped backward's last kernel when the call is one piece
-static bool one_piece(const DevShape& s, int64_t nnz, int64_t B) { return fast3_fits(s, nnz, B); }
 
-// small batches of an instantiated 3-core shape whose ids come with their bag boundaries: one wavefront per bag, MFMA per
-// id (ttemb_small3.inc) instead of the wave-per-id scalar kernels
-static bool use_small3(const DevShape& s, int64_t nnz, int64_t B, const int64_t* rowidx, const int64_t* offsets) {
-  const int path = current_path();
-  return (path == TTEMB_PATH_AUTO || path == TTEMB_PATH_PER_BAG) && rowidx == nullptr && offsets != nullptr && small3_supported(s) &&
-         !use_fast3(s, nnz, B, offsets != nullptr);
+// a 3-core shape (p, q, ranks r1 r2), through make_dev_shape; false when it has none (a core row too large)
+static bool shape3(const int p[3], const int q[3], int r1, int r2, DevShape* out) {
+  ttemb_shape_t t;
+  memset(&t, 0, sizeof(t));
+  t.T = 3;
+  for (int k = 0; k < 3; ++k) { t.p[k] = p[k]; t.q[k] = q[k]; }
+  t.R[0] = 1; t.R[1] = r1; t.R[2] = r2; t.R[3] = 1;
+  return make_dev_shape(&t, out) == TTEMB_OK;
 }
 
 // ---------------------------------------------------------------------------------
@@ -221,33 +221,15 @@ struct Merged4 {
 static bool view3(const DevShape& s, int a, DevShape* out) {   // the 3-core shape with cores a, a + 1 merged
   const long long pp = (long long)s.p[a] * s.p[a + 1], qq = (long long)s.q[a] * s.q[a + 1];
   if (pp > 0x7fffffffll || qq > 1024) return false;
-  DevShape d;
-  memset(&d, 0, sizeof(d));
-  d.T = 3;
-  int k = 0;
+  int p[3], q[3], R[3], k = 0;
   for (int t = 0; t < 4; ++t) {
     if (t == a + 1) continue;
-    d.p[k] = t == a ? (int)pp : s.p[t];
-    d.q[k] = t == a ? (int)qq : s.q[t];
-    d.R[k] = s.R[t];
+    p[k] = t == a ? (int)pp : s.p[t];
+    q[k] = t == a ? (int)qq : s.q[t];
+    R[k] = s.R[t];
     ++k;
   }
-  d.R[3] = 1;
-  d.D = s.D;
-  d.L[2] = 1; d.L[1] = d.p[2]; d.L[0] = (long long)d.p[1] * d.p[2];
-  long long Q = 1;
-  int pm = 0;
-  for (int t = 0; t < 3; ++t) {
-    Q *= d.q[t];
-    const long long rl = (long long)d.R[t] * d.q[t] * d.R[t + 1], pl = Q * d.R[t + 1];
-    if (rl > (1 << 24) || pl > (1 << 24)) return false;
-    d.row_len[t] = (int)rl;
-    d.part_len[t] = (int)pl;
-    if (t < 2 && d.part_len[t] > pm) pm = d.part_len[t];
-  }
-  d.part_max = pm;
-  *out = d;
-  return true;
+  return shape3(p, q, R[1], R[2], out);
 }
 
 // first choice: merge the first two cores (small virtual core, the per-id operand stays the last core); else the
@@ -257,27 +239,8 @@ static bool view3(const DevShape& s, int a, DevShape* out) {   // the 3-core sha
 // (a == -1 below).  The groups are the values of i0, the "prefix product" of a group is its G0 row, the gradient of
 // the identity is computed and dropped.  (FBTT/tt_embeddings_cuda.cu:757-779, :81-117 are the reference's 2-core forms.)
 static bool view_lifted2(const DevShape& s, DevShape* out) {
-  DevShape d;
-  memset(&d, 0, sizeof(d));
-  d.T = 3;
-  d.p[0] = s.p[0]; d.p[1] = 1; d.p[2] = s.p[1];
-  d.q[0] = s.q[0]; d.q[1] = 1; d.q[2] = s.q[1];
-  d.R[0] = 1; d.R[1] = s.R[1]; d.R[2] = s.R[1]; d.R[3] = 1;
-  d.D = s.D;
-  d.L[2] = 1; d.L[1] = d.p[2]; d.L[0] = (long long)d.p[1] * d.p[2];
-  long long Q = 1;
-  int pm = 0;
-  for (int t = 0; t < 3; ++t) {
-    Q *= d.q[t];
-    const long long rl = (long long)d.R[t] * d.q[t] * d.R[t + 1], pl = Q * d.R[t + 1];
-    if (rl > (1 << 24) || pl > (1 << 24)) return false;
-    d.row_len[t] = (int)rl;
-    d.part_len[t] = (int)pl;
-    if (t < 2 && d.part_len[t] > pm) pm = d.part_len[t];
-  }
-  d.part_max = pm;
-  *out = d;
-  return true;
+  const int p[3] = {s.p[0], 1, s.p[1]}, q[3] = {s.q[0], 1, s.q[1]};
+  return shape3(p, q, s.R[1], s.R[1], out);
 }
 
 // per_bag_ok: the call could run on the per-bag kernels (ids + offsets, no row index; sizing queries pass true): a 2- or
@@ -362,14 +325,8 @@ static Padded3 pad_ranks(const DevShape& s, int64_t nnz, int64_t B, bool have_of
   if (s.T != 3 || path == TTEMB_PATH_GENERIC || path == TTEMB_PATH_PER_BAG || fast3_supported(s)) return pd;
   const int need = s.R[1] > s.R[2] ? s.R[1] : s.R[2];
   for (int R : {8, 16, 32, 64, 128, 256}) {
-    if (R < need) continue;
-    ttemb_shape_t t;
-    memset(&t, 0, sizeof(t));
-    t.T = 3;
-    for (int k = 0; k < 3; ++k) { t.p[k] = s.p[k]; t.q[k] = s.q[k]; }
-    t.R[0] = 1; t.R[1] = R; t.R[2] = R; t.R[3] = 1;
     DevShape d;
-    if (make_dev_shape(&t, &d) != TTEMB_OK || !fast3_supported(d)) continue;
+    if (R < need || !shape3(s.p, s.q, R, R, &d) || !fast3_supported(d)) continue;
     if (!use_fast3(d, nnz, B, have_offsets)) return pd;   // (a larger rank of the list would pay even later)
     pd.on = true;
     pd.sp = d;
@@ -380,6 +337,62 @@ static Padded3 pad_ranks(const DevShape& s, int64_t nnz, int64_t B, bool have_of
     return pd;
   }
   return pd;
+}
+
+// ---------------------------------------------------------------------------------
+// The route of a lookup: which kernels run, on which 3-core shape, decided once per call (and per size query) from the shape,
+// the size, what the call carries and the forced path.  The kinds are disjoint by shape: GROUPED is a 3-core table of an
+// instantiated grouped shape, PADDED one whose ranks are padded up to one, MERGED a 2- or 4-core table on a 3-core view;
+// PER_BAG and SCALAR take what is left.
+// ---------------------------------------------------------------------------------
+enum RouteKind { kGrouped, kMerged, kPadded, kPerBag, kScalar };
+struct Route {
+  RouteKind kind;
+  DevShape s3;     // the shape the 3-core call runs on: the table's own, the merged view (m4.s3) or the padded table (pd.sp)
+  bool grouped;    // the 3-core call runs on the grouped kernels (else on the per-bag or the scalar ones)
+  Merged4 m4;      // kMerged: the virtual core
+  Padded3 pd;      // kPadded: the padded cores
+};
+
+// have_offsets: the ids come with their bag boundaries (what a call past one row window needs to run in pieces); per_bag_ok:
+// ... and without a row index (what the per-bag kernels need); views_ok = false: neither the grouped kernels nor a view (an
+// empty forward)
+static Route route_of(const DevShape& ds, int64_t nnz, int64_t B, bool have_offsets, bool per_bag_ok, bool views_ok = true) {
+  Route r;
+  memset(&r, 0, sizeof(r));
+  r.kind = kScalar;
+  r.s3 = ds;
+  const int path = current_path();
+  if (views_ok && use_fast3(ds, nnz, B, have_offsets)) {
+    r.kind = kGrouped;
+    r.grouped = true;
+  } else if (views_ok && (r.m4 = merge_first_two(ds, nnz, B, per_bag_ok, have_offsets)).on) {
+    r.kind = kMerged;
+    r.s3 = r.m4.s3;
+    r.grouped = !r.m4.per_bag;
+  } else if (views_ok && (r.pd = pad_ranks(ds, nnz, B, have_offsets)).on) {
+    r.kind = kPadded;
+    r.s3 = r.pd.sp;
+    r.grouped = true;
+  } else if (per_bag_ok && (path == TTEMB_PATH_AUTO || path == TTEMB_PATH_PER_BAG) && small3_supported(ds)) {
+    r.kind = kPerBag;   // small batches: one wavefront per bag, MFMA per id (ttemb_small3.inc) instead of the scalar kernels
+  }
+  return r;
+}
+
+static const char* view_name(const Route& r) { return r.kind == kMerged ? "merged core" : "padded cores"; }
+
+// what a view keeps in front of the grouped kernels' region: V / the padded cores, and (backward) their gradients behind them
+static int64_t view_bytes(const Route& r, bool bwd) {
+  const int64_t one = r.kind == kMerged ? r.m4.v_bytes : (r.kind == kPadded ? r.pd.cores_total : 0);
+  return bwd ? 2 * one : one;
+}
+
+// a lookup's workspace: [header | gradient scratch (backward) | row slot | view_bytes | the grouped kernels' region]
+static int64_t lookup_workspace_bytes(const Route& r, const DevShape& ds, int32_t op, int64_t nnz, int64_t B) {
+  const bool bwd = op == TTEMB_OP_BACKWARD;
+  return kFast3HeaderBytes + (bwd ? grad_scratch_bytes(ds) : 0) + align256(nnz * 8) + view_bytes(r, bwd) +
+         (r.grouped ? fast3_workspace_bytes(r.s3, op, nnz, B) : 0);
 }
 
 // dst[row][a][j][b] (ranks Ra x Rb) = src[row][a][j][b] inside the original ranks (ra x rb), 0 outside -- and back
@@ -543,12 +556,27 @@ static int build_merged_core(const Merged4& m, const CorePtrs& cp, float* V, hip
   return check_hip(hipGetLastError(), "merge_pair_kernel");
 }
 
-// the 3-core operand lists of a merged table: V in the place of the pair
-static void merged_cores(const Merged4& m, const CorePtrs& cp, const float* V, CorePtrs* c3) {
+// the 3-core operand (or gradient) lists of a merged table: V (dV) in the place of the pair (the identity's gradient is dropped)
+template <class Ptrs>
+static void merged_cores(const Merged4& m, const Ptrs& cp, float* V, Ptrs* c3) {
   memset(c3, 0, sizeof(*c3));
   if (m.a < 0) { c3->c[0] = cp.c[0]; c3->c[1] = V; c3->c[2] = cp.c[1]; }
   else if (m.a == 0) { c3->c[0] = V; c3->c[1] = cp.c[2]; c3->c[2] = cp.c[3]; }
   else          { c3->c[0] = cp.c[0]; c3->c[1] = cp.c[1]; c3->c[2] = V; }
+}
+
+// the prologue of a route: V (the merged pair, or the lifted table's identity) / the padded cores at `buf`; *c3: the operands of
+// the 3-core call.  build = false (the id-only half of a forward): the operands' places only, nothing launched
+static int build_view(const Route& r, const DevShape& ds, const CorePtrs& cp, char* buf, bool build, CorePtrs* c3, hipStream_t st) {
+  *c3 = cp;
+  if (r.kind == kMerged) {
+    merged_cores(r.m4, cp, reinterpret_cast<float*>(buf), c3);
+    return build ? build_merged_core(r.m4, cp, reinterpret_cast<float*>(buf), st) : TTEMB_OK;
+  }
+  if (r.kind != kPadded) return TTEMB_OK;
+  if (build) return build_padded_cores(ds, r.pd, cp, buf, c3, st);
+  memset(c3, 0, sizeof(*c3));
+  return TTEMB_OK;
 }
 
 __global__ void zero_words_kernel(uint32_t* __restrict__ p, size_t n) {
@@ -702,91 +730,84 @@ static int check_lookup_args(const void* cores, const void* indices, int64_t nnz
   return TTEMB_OK;
 }
 
-// rows of the ids: the caller's rowidx, or (rowidx == NULL) derived from offsets into the head
-// of the workspace; *ws / *ws_bytes are advanced past the part used
-static int resolve_rowidx(const int64_t** rowidx, const int64_t* offsets, int64_t nnz, int64_t B, char** ws,
-                          int64_t* ws_bytes, hipStream_t st, bool rows_in_plan = false) {
-  const int64_t need = align256(nnz * 8);
-  char* base = *ws;
-  if (base != nullptr && *ws_bytes >= need) {
-    *ws = base + need;
-    *ws_bytes -= need;
-  } else if (*rowidx == nullptr && nnz > 0) {
-    return fail(TTEMB_E_WORKSPACE, "workspace too small for the row index (%lld bytes)", (long long)need);
-  }
-  if (*rowidx != nullptr || nnz == 0) return TTEMB_OK;
-  if (offsets == nullptr) return fail(TTEMB_E_BADARG, "rowidx and offsets are both null");
-  return TTEMB_OK;   // both kernel families derive the rows from `offsets` themselves (no expansion launch, no array)
+// what every lookup entry point starts with: no pending device fault, a valid shape and sizes, the core pointers, and the
+// workspace split into the header (the grouped path's persistent words: the first kFast3HeaderBytes of every lookup
+// workspace; null when the workspace is smaller) and the rest
+struct Entry {
+  DevShape ds;
+  CorePtrs cp;
+  void* header;
+  char* ws;
+  int64_t ws_bytes;
+  hipStream_t st;
+};
+static int enter(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices, int64_t nnz, int64_t B,
+                 void* workspace, int64_t workspace_bytes, void* stream, Entry* e) {
+  int rc = pending_device_fault();
+  if (rc) return rc;
+  rc = make_dev_shape(shape, &e->ds);
+  if (rc) return rc;
+  rc = check_lookup_args(cores, indices, nnz, B);
+  if (rc) return rc;
+  for (int t = 0; t < TTEMB_MAX_CORES; ++t) e->cp.c[t] = t < e->ds.T ? cores[t] : nullptr;
+  const int64_t h = workspace != nullptr && workspace_bytes >= kFast3HeaderBytes ? kFast3HeaderBytes : 0;
+  e->header = h ? workspace : nullptr;
+  e->ws = reinterpret_cast<char*>(workspace) + h;
+  e->ws_bytes = workspace_bytes - h;
+  e->st = reinterpret_cast<hipStream_t>(stream);
+  return TTEMB_OK;
 }
 
-// shared body of the three backward entry points: gradient of the live ids into `dst`
-static int backward_into(const DevShape& ds, const CorePtrs& cp, const int64_t* indices,
-                         const int64_t* rowidx, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B,
-                         const float* d_output, const CorePtrsMut& dst, void* ws, int64_t ws_bytes,
-                         const void* plan, int64_t plan_bytes, hipStream_t st, void* header, const FusedUpdate* update = nullptr,
-                         bool* grouped = nullptr) {
-  // *grouped: the gradients come from a grouped backward, whose finalize kernel left its verdict in the header's poison word
-  if (grouped != nullptr) *grouped = false;
-  if (use_fast3(ds, nnz, B, offsets != nullptr)) {
-    if (grouped != nullptr) *grouped = true;
-    return launch_backward_fast3(ds, cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, dst, ws, ws_bytes, plan,
-                                 plan_bytes, st, update, header);
+// the row-index slot at the head of the workspace (part of the layout on every route; both kernel families derive the rows
+// from `offsets` themselves when rowidx is null -- no expansion launch, no array); *ws / *ws_bytes are advanced past it
+static int resolve_rowidx(const int64_t* rowidx, const int64_t* offsets, int64_t nnz, char** ws, int64_t* ws_bytes) {
+  const int64_t need = align256(nnz * 8);
+  if (*ws != nullptr && *ws_bytes >= need) {
+    *ws += need;
+    *ws_bytes -= need;
+  } else if (rowidx == nullptr && nnz > 0) {
+    return fail(TTEMB_E_WORKSPACE, "workspace too small for the row index (%lld bytes)", (long long)need);
   }
-  const Merged4 m4 = merge_first_two(ds, nnz, B, rowidx == nullptr && offsets != nullptr, offsets != nullptr);
-  if (m4.on) {   // 4 cores: the 3-core backward on (V, G2, G3), then dV back onto G0 and G1
-    if (grouped != nullptr) *grouped = !m4.per_bag;
-    if (ws == nullptr || ws_bytes < 2 * m4.v_bytes) return fail(TTEMB_E_WORKSPACE, "backward needs room for the merged core");
-    float* V = reinterpret_cast<float*>(ws);
-    float* dV = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + m4.v_bytes);
-    int rc = build_merged_core(m4, cp, V, st);
-    if (rc) return rc;
-    CorePtrs c3;
-    CorePtrsMut d3;
-    merged_cores(m4, cp, V, &c3);
-    memset(&d3, 0, sizeof(d3));
-    if (m4.a < 0) { d3.c[0] = dst.c[0]; d3.c[1] = dV; d3.c[2] = dst.c[1]; }   // (the identity's gradient is dropped)
-    else if (m4.a == 0) { d3.c[0] = dV; d3.c[1] = dst.c[2]; d3.c[2] = dst.c[3]; }
-    else           { d3.c[0] = dst.c[0]; d3.c[1] = dst.c[1]; d3.c[2] = dV; }
-    if (m4.per_bag) {   // the per-bag kernels ADD into the gradients: clear them (the real cores, then dV)
-      rc = launch_zero_cores(ds, dst, st);
-      if (rc == TTEMB_OK) rc = launch_zero(dV, (size_t)m4.v_bytes, st, "zero dV");
-      if (rc == TTEMB_OK) rc = launch_backward_small3(m4.s3, c3, indices, offsets, nnz, nnz_dev, B, d_output, d3, st);
-    } else {
-      rc = launch_backward_fast3(m4.s3, c3, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, d3,
-                                 reinterpret_cast<char*>(ws) + 2 * m4.v_bytes, ws_bytes - 2 * m4.v_bytes, plan, plan_bytes, st, nullptr, header);
-    }
-    if (rc || m4.a < 0) return rc;
-    hipLaunchKernelGGL(split_pair_kernel, dim3((unsigned)(m4.pa + m4.pb), (unsigned)m4.K), dim3(256), 0, st, cp.c[m4.a], cp.c[m4.a + 1], dV, m4.pa,
-                       m4.pb, m4.rows, m4.K, m4.n, dst.c[m4.a], dst.c[m4.a + 1]);
-    return check_hip(hipGetLastError(), "split_pair_kernel");
-  }
-  const Padded3 pd = pad_ranks(ds, nnz, B, offsets != nullptr);
-  if (pd.on) {   // ranks off the list: grouped backward on the padded cores, then the original sub-block of its gradient
-    if (update != nullptr) return fail(TTEMB_E_BADARG, "internal: a padded table writes gradients, the step follows");
-    if (grouped != nullptr) *grouped = true;
-    if (ws == nullptr || ws_bytes < 2 * pd.cores_total) return fail(TTEMB_E_WORKSPACE, "backward needs room for the padded cores");
-    char* wp = reinterpret_cast<char*>(ws);
-    CorePtrs cp3;
-    int rc = build_padded_cores(ds, pd, cp, wp, &cp3, st);
-    if (rc) return rc;
-    CorePtrsMut d3;
-    memset(&d3, 0, sizeof(d3));
-    int64_t off = pd.cores_total;
-    for (int t = 0; t < 3; ++t) {
-      d3.c[t] = reinterpret_cast<float*>(wp + off);
-      off += pd.core_bytes[t];
-    }
-    rc = launch_backward_fast3(pd.sp, cp3, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, d3, wp + 2 * pd.cores_total,
-                               ws_bytes - 2 * pd.cores_total, plan, plan_bytes, st, nullptr, header);
-    if (rc) return rc;
-    return unpad_grads(ds, pd, d3, dst, st);
-  }
-  if (current_path() == TTEMB_PATH_FAST3) return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-  int rc = launch_zero_cores(ds, dst, st);
+  if (rowidx == nullptr && offsets == nullptr && nnz > 0) return fail(TTEMB_E_BADARG, "rowidx and offsets are both null");
+  return TTEMB_OK;
+}
+
+// shared body of the three backward entry points: gradient of the live ids into `dst` on route `r` -- prologue (V / the padded
+// cores), one 3-core call, epilogue (dV back onto the pair / the original sub-block of the padded gradient).  `update`: the step
+// the grouped backward's last kernel applies (only a GROUPED call of one piece is given one)
+static int backward_into(const Route& r, const DevShape& ds, const CorePtrs& cp, const int64_t* indices, const int64_t* rowidx,
+                         const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, const float* d_output,
+                         const CorePtrsMut& dst, char* ws, int64_t ws_bytes, const void* plan, int64_t plan_bytes, hipStream_t st,
+                         void* header, const FusedUpdate* update = nullptr) {
+  if (r.kind == kPadded && update != nullptr) return fail(TTEMB_E_BADARG, "internal: a padded table writes gradients, the step follows");
+  if (r.kind == kScalar && current_path() == TTEMB_PATH_FAST3) return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
+  const int64_t vb = view_bytes(r, true);   // [V | dV] / [padded cores | their gradients] in front of the grouped kernels' region
+  if (vb > 0 && (ws == nullptr || ws_bytes < vb)) return fail(TTEMB_E_WORKSPACE, "backward needs room for the %s", view_name(r));
+  CorePtrs c3;
+  int rc = build_view(r, ds, cp, ws, true, &c3, st);
   if (rc) return rc;
-  if (use_small3(ds, nnz, B, rowidx, offsets))
-    return launch_backward_small3(ds, cp, indices, offsets, nnz, nnz_dev, B, d_output, dst, st);
-  return launch_backward_generic(ds, cp, indices, rowidx, offsets, B, nnz, nnz_dev, d_output, dst, st);
+  char* grads = ws + vb / 2;
+  CorePtrsMut d3 = dst;
+  if (r.kind == kMerged) merged_cores(r.m4, dst, reinterpret_cast<float*>(grads), &d3);
+  int64_t off = 0;
+  for (int t = 0; r.kind == kPadded && t < 3; off += r.pd.core_bytes[t++]) d3.c[t] = reinterpret_cast<float*>(grads + off);
+  if (!r.grouped) {   // the per-bag and scalar kernels ADD into the gradients: clear them (the real cores, then dV)
+    rc = launch_zero_cores(ds, dst, st);
+    if (rc == TTEMB_OK && r.kind == kMerged) rc = launch_zero(grads, (size_t)r.m4.v_bytes, st, "zero dV");
+    if (rc == TTEMB_OK)
+      rc = r.kind == kScalar ? launch_backward_generic(ds, cp, indices, rowidx, offsets, B, nnz, nnz_dev, d_output, dst, st)
+                             : launch_backward_small3(r.s3, c3, indices, offsets, nnz, nnz_dev, B, d_output, d3, st);
+  } else {
+    rc = launch_backward_fast3(r.s3, c3, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, d3, ws + vb, ws_bytes - vb, plan,
+                               plan_bytes, st, r.kind == kGrouped ? update : nullptr, header);
+  }
+  if (rc) return rc;
+  if (r.kind == kPadded) return unpad_grads(ds, r.pd, d3, dst, st);
+  if (r.kind != kMerged || r.m4.a < 0) return TTEMB_OK;
+  const Merged4& m4 = r.m4;
+  hipLaunchKernelGGL(split_pair_kernel, dim3((unsigned)(m4.pa + m4.pb), (unsigned)m4.K), dim3(256), 0, st, cp.c[m4.a], cp.c[m4.a + 1],
+                     reinterpret_cast<const float*>(grads), m4.pa, m4.pb, m4.rows, m4.K, m4.n, dst.c[m4.a], dst.c[m4.a + 1]);
+  return check_hip(hipGetLastError(), "split_pair_kernel");
 }
 
 }  // namespace ttemb
@@ -890,29 +911,15 @@ int64_t ttemb_workspace_bytes(const ttemb_shape_t* shape, int32_t op, int64_t nn
   DevShape ds;
   int rc = make_dev_shape(shape, &ds);
   if (rc) return rc;
-  const bool f3 = use_fast3(ds, op == TTEMB_OP_CACHE_POPULATE ? B : nnz, B);
-  const Merged4 m4 = op == TTEMB_OP_CACHE_POPULATE ? Merged4{} : merge_first_two(ds, nnz, B, true);
-  // every lookup op's workspace begins with the header the grouped path keeps its few persistent words in
-  const Padded3 pd = (op == TTEMB_OP_CACHE_POPULATE || f3 || m4.on) ? Padded3{} : pad_ranks(ds, nnz, B, true);
-  if (pd.on && op == TTEMB_OP_FORWARD)
-    return kFast3HeaderBytes + align256(nnz * 8) + pd.cores_total + fast3_workspace_bytes(pd.sp, op, nnz, B);
-  if (pd.on && op == TTEMB_OP_BACKWARD)
-    return kFast3HeaderBytes + grad_scratch_bytes(ds) + align256(nnz * 8) + 2 * pd.cores_total + fast3_workspace_bytes(pd.sp, op, nnz, B);
-  switch (op) {
-    case TTEMB_OP_FORWARD:
-      if (m4.on) return kFast3HeaderBytes + align256(nnz * 8) + m4.v_bytes + (m4.per_bag ? 0 : fast3_workspace_bytes(m4.s3, op, nnz, B));
-      return kFast3HeaderBytes + align256(nnz * 8) + (f3 ? fast3_workspace_bytes(ds, op, nnz, B) : 0);
-    case TTEMB_OP_BACKWARD:
-      if (m4.on) return kFast3HeaderBytes + grad_scratch_bytes(ds) + align256(nnz * 8) + 2 * m4.v_bytes + (m4.per_bag ? 0 : fast3_workspace_bytes(m4.s3, op, nnz, B));
-      return kFast3HeaderBytes + grad_scratch_bytes(ds) + align256(nnz * 8) + (f3 ? fast3_workspace_bytes(ds, op, nnz, B) : 0);
-    case TTEMB_OP_CACHE_POPULATE: {
-      const int64_t sort = populate_workspace_bytes(nnz);
-      if (sort < 0) return fail(TTEMB_E_HIP, "rocprim size query failed");
-      return kFast3HeaderBytes + sort + (f3 ? fast3_workspace_bytes(ds, TTEMB_OP_FORWARD, B, B) : 0);
-    }
-    default:
-      return fail(TTEMB_E_BADARG, "unknown op %d", op);
+  if (op == TTEMB_OP_CACHE_POPULATE) {   // the sort, and room for a grouped forward of the B rows
+    const int64_t sort = populate_workspace_bytes(nnz);
+    if (sort < 0) return fail(TTEMB_E_HIP, "rocprim size query failed");
+    const bool grouped = route_of(ds, B, B, true, true).kind == kGrouped;
+    return kFast3HeaderBytes + sort + (grouped ? fast3_workspace_bytes(ds, TTEMB_OP_FORWARD, B, B) : 0);
   }
+  if (op != TTEMB_OP_FORWARD && op != TTEMB_OP_BACKWARD) return fail(TTEMB_E_BADARG, "unknown op %d", op);
+  // (sized for ids with offsets and without a row index: the call may take any route)
+  return lookup_workspace_bytes(route_of(ds, nnz, B, true, true), ds, op, nnz, B);
 }
 
 int ttemb_kernel_family(const ttemb_shape_t* shape, int64_t nnz, int64_t B, int32_t ids_with_offsets) {
@@ -920,22 +927,14 @@ int ttemb_kernel_family(const ttemb_shape_t* shape, int64_t nnz, int64_t B, int3
   int rc = make_dev_shape(shape, &ds);
   if (rc) return rc;
   if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "negative size");
-  auto family3 = [nnz, B](const DevShape& s, bool grouped) {
-    if (grouped) return fast3_wide(s) ? (int)TTEMB_FAMILY_GROUPED_WIDE : (TTEMB_FAMILY_GROUPED | (fast3_prefix_in_chain(s, nnz, B) ? TTEMB_FAMILY_PREFIX_IN_CHAIN : 0) |
-                                                                          (fast3_group_products_in_chain(s, nnz, B) ? TTEMB_FAMILY_GROUP_PRODUCTS_IN_CHAIN : 0));
-    return small3_templated_shape(s) ? (int)TTEMB_FAMILY_PER_BAG : (int)TTEMB_FAMILY_PER_BAG_RT;
-  };
   // (without the bag boundaries a call past one row window cannot be cut into pieces)
-  if (use_fast3(ds, nnz, B, ids_with_offsets != 0)) return family3(ds, true);
-  const Merged4 m4 = merge_first_two(ds, nnz, B, ids_with_offsets != 0, ids_with_offsets != 0);
-  if (m4.on) return family3(m4.s3, !m4.per_bag) | TTEMB_FAMILY_MERGED;
-  const Padded3 pd = pad_ranks(ds, nnz, B, ids_with_offsets != 0);
-  if (pd.on) return family3(pd.sp, true) | TTEMB_FAMILY_PADDED;
-  // use_small3 with stand-in pointers: only their null-ness is looked at
-  const int64_t* none = nullptr;
-  const int64_t* some = reinterpret_cast<const int64_t*>(&ds);
-  if (use_small3(ds, nnz, B, ids_with_offsets ? none : some, ids_with_offsets ? some : none)) return family3(ds, false);
-  return TTEMB_FAMILY_SCALAR;
+  const Route r = route_of(ds, nnz, B, ids_with_offsets != 0, ids_with_offsets != 0);
+  if (r.kind == kScalar) return TTEMB_FAMILY_SCALAR;
+  const int view = r.kind == kMerged ? TTEMB_FAMILY_MERGED : (r.kind == kPadded ? TTEMB_FAMILY_PADDED : 0);
+  if (!r.grouped) return view | (small3_templated_shape(r.s3) ? TTEMB_FAMILY_PER_BAG : TTEMB_FAMILY_PER_BAG_RT);
+  if (fast3_wide(r.s3)) return view | TTEMB_FAMILY_GROUPED_WIDE;
+  return view | TTEMB_FAMILY_GROUPED | (fast3_prefix_in_chain(r.s3, nnz, B) ? TTEMB_FAMILY_PREFIX_IN_CHAIN : 0) |
+         (fast3_group_products_in_chain(r.s3, nnz, B) ? TTEMB_FAMILY_GROUP_PRODUCTS_IN_CHAIN : 0);
 }
 
 int64_t ttemb_plan_bytes(const ttemb_shape_t* shape, int64_t nnz) {
@@ -943,111 +942,62 @@ int64_t ttemb_plan_bytes(const ttemb_shape_t* shape, int64_t nnz) {
   int rc = make_dev_shape(shape, &ds);
   if (rc) return rc;
   if (nnz < 0) return fail(TTEMB_E_BADARG, "negative size");
-  // (a call that runs in pieces keeps no plan -- a plan describes one piece --; neither does a per-bag view)
-  if (use_fast3(ds, nnz, 0)) return fast3_fits(ds, nnz, 0) ? fast3_plan_bytes(ds, nnz) : 0;
-  const Merged4 m4 = merge_first_two(ds, nnz, 0);
-  if (m4.on) return fast3_fits(m4.s3, nnz, 0) ? fast3_plan_bytes(m4.s3, nnz) : 0;
-  const Padded3 pd = pad_ranks(ds, nnz, 0, true);   // ranks off the list: the plan of the padded table
-  return pd.on && fast3_fits(pd.sp, nnz, 0) ? fast3_plan_bytes(pd.sp, nnz) : 0;
+  // the plan of the 3-core call (a call that runs in pieces keeps none -- a plan describes one piece --; neither does a per-bag view)
+  const Route r = route_of(ds, nnz, 0, true, false);
+  return r.grouped && fast3_fits(r.s3, nnz, 0) ? fast3_plan_bytes(r.s3, nnz) : 0;
 }
 
 }  // extern "C"
 
 // phase 0 = the whole forward; 1 = everything that depends only on the ids; 2 = the rest (reads the cores)
+// prologue (V / the padded cores), one 3-core call; the workspace behind the header: [row slot | view_bytes | grouped region]
 static int forward_phase(int phase, const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices,
                          const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
                          const int32_t* nnz_dev, int64_t B, float* output, void* workspace,
                          int64_t workspace_bytes, void* plan, int64_t plan_bytes, void* stream) {
-  DevShape ds;
-  int rc = pending_device_fault();
-  if (rc) return rc;
-  rc = make_dev_shape(shape, &ds);
-  if (rc) return rc;
-  rc = check_lookup_args(cores, indices, nnz, B);
+  Entry e;
+  int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
   if (B == 0) return TTEMB_OK;
   if (output == nullptr) return fail(TTEMB_E_BADARG, "output is null");
   if (B >= 0x7fffffffll) return fail(TTEMB_E_BADARG, "B exceeds int32 range");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  CorePtrs cp;
-  for (int t = 0; t < TTEMB_MAX_CORES; ++t) cp.c[t] = t < ds.T ? cores[t] : nullptr;
-  void* header = nullptr;   // the grouped path's persistent words: the first kFast3HeaderBytes of every lookup workspace
-  if (workspace != nullptr && workspace_bytes >= kFast3HeaderBytes) {
-    header = workspace;
-    workspace = reinterpret_cast<char*>(workspace) + kFast3HeaderBytes;
-    workspace_bytes -= kFast3HeaderBytes;
-  }
-  const Merged4 m4 = nnz > 0 ? merge_first_two(ds, nnz, B, rowidx == nullptr && offsets != nullptr, offsets != nullptr) : Merged4{};
-  if (m4.on && m4.per_bag && phase == 1) return TTEMB_OK;   // the per-bag kernels have no id-only half
-  if (m4.on) {   // 4 cores through the 3-core kernels on (V = G0.G1, G2, G3); workspace: [row slot | V | 3-core]
-    char* w4 = reinterpret_cast<char*>(workspace);
-    const int64_t head = align256(nnz * 8);
-    if (w4 == nullptr || workspace_bytes < head + m4.v_bytes) return fail(TTEMB_E_WORKSPACE, "forward needs room for the merged core");
-    if (rowidx == nullptr && offsets == nullptr) return fail(TTEMB_E_BADARG, "rowidx and offsets are both null");
-    float* V = reinterpret_cast<float*>(w4 + head);
-    CorePtrs c3;
-    merged_cores(m4, cp, V, &c3);
-    if (phase != 1) {
-      rc = build_merged_core(m4, cp, V, st);
-      if (rc) return rc;
-    }
-    if (m4.per_bag)   // one launch, every output row written once
-      return launch_forward_small3(m4.s3, c3, indices, offsets, nnz, nnz_dev, B, output, st);
-    if (phase != 2 && offsets == nullptr) {
-      rc = launch_zero(output, (size_t)B * ds.D * 4, st, "zero output");
-      if (rc) return rc;
-    }
-    return launch_forward_fast3(m4.s3, c3, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr,
-                                w4 + head + m4.v_bytes, workspace_bytes - head - m4.v_bytes, plan, plan_bytes, phase, st, header);
-  }
-  const bool f3 = nnz > 0 && use_fast3(ds, nnz, B, offsets != nullptr);
-  const Padded3 pd = (nnz > 0 && !f3) ? pad_ranks(ds, nnz, B, offsets != nullptr) : Padded3{};
-  if (pd.on) {   // ranks off the instantiated list: the grouped kernels on zero-padded cores; workspace: [row slot | padded cores | grouped]
-    char* wp = reinterpret_cast<char*>(workspace);
-    const int64_t head = align256(nnz * 8);
-    if (wp == nullptr || workspace_bytes < head + pd.cores_total) return fail(TTEMB_E_WORKSPACE, "forward needs room for the padded cores");
-    if (rowidx == nullptr && offsets == nullptr) return fail(TTEMB_E_BADARG, "rowidx and offsets are both null");
-    CorePtrs cp3;
-    memset(&cp3, 0, sizeof(cp3));
-    if (phase != 1) {   // (the id-only half does not read the cores)
-      rc = build_padded_cores(ds, pd, cp, wp + head, &cp3, st);
-      if (rc) return rc;
-    }
-    if (phase != 2 && offsets == nullptr) {
-      rc = launch_zero(output, (size_t)B * ds.D * 4, st, "zero output");
-      if (rc) return rc;
-    }
-    return launch_forward_fast3(pd.sp, cp3, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr,
-                                wp + head + pd.cores_total, workspace_bytes - head - pd.cores_total, plan, plan_bytes, phase, st, header);
-  }
-  if (phase == 1 && !f3) return TTEMB_OK;   // the generic kernels have no id-only half: phase 2 is their whole forward
-  if (phase == 2 && f3) {
-    return launch_forward_fast3(ds, cp, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr, workspace,
-                                workspace_bytes, plan, plan_bytes, 2, reinterpret_cast<hipStream_t>(stream), header);
-  }
+  const DevShape& ds = e.ds;
+  const Route r = route_of(ds, nnz, B, offsets != nullptr, rowidx == nullptr && offsets != nullptr, nnz > 0);
+  if (phase == 1 && !r.grouped) return TTEMB_OK;   // the per-bag and scalar kernels have no id-only half: phase 2 is their whole forward
+  if (phase == 2 && r.kind == kGrouped)   // (on the workspace as it is handed over: the row slot is the id-only half's business)
+    return launch_forward_fast3(ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr, e.ws, e.ws_bytes,
+                                plan, plan_bytes, 2, e.st, e.header);
+  const int64_t vb = view_bytes(r, false);
+  if (vb > 0 && (e.ws == nullptr || e.ws_bytes < align256(nnz * 8) + vb))
+    return fail(TTEMB_E_WORKSPACE, "forward needs room for the %s", view_name(r));
   if (rowidx == nullptr && offsets == nullptr && nnz > 0) return fail(TTEMB_E_BADARG, "rowidx and offsets are both null");
-  if (!f3 && use_small3(ds, nnz, B, rowidx, offsets))   // one launch: every output row written once, zeros for an empty bag
-    return launch_forward_small3(ds, cp, indices, offsets, nnz, nnz_dev, B, output, st);
-  char* ws = reinterpret_cast<char*>(workspace);
-  // the row-index slot at the head of the workspace is part of the layout on both paths; the fast path derives
-  // rows (and clears the rows of bags that do not hold exactly one id) inside its grouping pass
-  rc = resolve_rowidx(&rowidx, offsets, nnz, B, &ws, &workspace_bytes, st, f3);
+  char* ws = e.ws;
+  int64_t ws_bytes = e.ws_bytes;
+  CorePtrs c3;
+  rc = build_view(r, ds, e.cp, vb > 0 ? ws + align256(nnz * 8) : ws, phase != 1, &c3, e.st);   // (the id-only half does not read the cores)
   if (rc) return rc;
-  workspace = ws;
-  if (offsets == nullptr) {
-    rc = launch_zero(output, (size_t)B * ds.D * 4, st, "zero output");
-  } else if (!f3) {
+  if (!r.grouped && r.kind != kScalar)   // per-bag: one launch, every output row written once, zeros for an empty bag
+    return launch_forward_small3(r.s3, c3, indices, offsets, nnz, nnz_dev, B, output, e.st);
+  rc = resolve_rowidx(rowidx, offsets, nnz, &ws, &ws_bytes);
+  if (rc) return rc;
+  ws += vb;
+  ws_bytes -= vb;
+  // the rows the kernels add into: every row without offsets (the lookup half of a grouped forward finds them cleared by the id-only
+  // half); with offsets those of bags that do not hold exactly one id -- the grouping pass clears them itself
+  if (offsets == nullptr && !(phase == 2 && r.grouped)) {
+    rc = launch_zero(output, (size_t)B * ds.D * 4, e.st, "zero output");
+  } else if (offsets != nullptr && !r.grouped) {
     const int threads = 256;
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((B + threads - 1) / threads)), dim3(threads), 0,
-                       st, offsets, B, ds.D, output);
+                       e.st, offsets, B, ds.D, output);
     rc = check_hip(hipGetLastError(), "zero_rows_kernel");
   }
   if (rc || nnz == 0) return rc;
-  if (f3)
-    return launch_forward_fast3(ds, cp, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr, workspace,
-                                workspace_bytes, plan, plan_bytes, phase, st, header);
+  if (r.grouped)
+    return launch_forward_fast3(r.s3, c3, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr, ws, ws_bytes, plan,
+                                plan_bytes, phase, e.st, e.header);
   if (current_path() == TTEMB_PATH_FAST3) return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-  return launch_forward_generic(ds, cp, indices, rowidx, offsets, B, nnz, nnz_dev, output, st);
+  return launch_forward_generic(ds, e.cp, indices, rowidx, offsets, B, nnz, nnz_dev, output, e.st);
 }
 
 extern "C" {
@@ -1085,36 +1035,21 @@ int ttemb_backward_dense(const ttemb_shape_t* shape, const float* const* cores,
                          float* const* d_cores, void* workspace, int64_t workspace_bytes,
                          const void* plan, int64_t plan_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_dense");
-  DevShape ds;
-  int rc = pending_device_fault();
-  if (rc) return rc;
-  rc = make_dev_shape(shape, &ds);
-  if (rc) return rc;
-  rc = check_lookup_args(cores, indices, nnz, B);
+  Entry e;
+  int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
   if (d_cores == nullptr) return fail(TTEMB_E_BADARG, "d_cores is null");
   if (nnz > 0 && d_output == nullptr) return fail(TTEMB_E_BADARG, "d_output is null");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  CorePtrs cp;
   CorePtrsMut dp;
-  for (int t = 0; t < TTEMB_MAX_CORES; ++t) {
-    cp.c[t] = t < ds.T ? cores[t] : nullptr;
-    dp.c[t] = t < ds.T ? d_cores[t] : nullptr;
-  }
-  void* header = nullptr;   // the grouped path's persistent words: the first kFast3HeaderBytes of every lookup workspace
-  if (workspace != nullptr && workspace_bytes >= kFast3HeaderBytes) {
-    header = workspace;
-    workspace = reinterpret_cast<char*>(workspace) + kFast3HeaderBytes;
-    workspace_bytes -= kFast3HeaderBytes;
-  }
+  for (int t = 0; t < TTEMB_MAX_CORES; ++t) dp.c[t] = t < e.ds.T ? d_cores[t] : nullptr;
   // the gradient scratch region behind the header is unused in dense mode
-  const int64_t skip = grad_scratch_bytes(ds);
-  char* ws = reinterpret_cast<char*>(workspace);
-  int64_t rest = workspace_bytes > skip ? workspace_bytes - skip : 0;
-  ws = ws ? ws + skip : nullptr;
-  rc = resolve_rowidx(&rowidx, offsets, nnz, B, &ws, &rest, st, use_fast3(ds, nnz, B, offsets != nullptr));
+  const int64_t skip = grad_scratch_bytes(e.ds);
+  char* ws = e.ws ? e.ws + skip : nullptr;
+  int64_t rest = e.ws_bytes > skip ? e.ws_bytes - skip : 0;
+  rc = resolve_rowidx(rowidx, offsets, nnz, &ws, &rest);
   if (rc) return rc;
-  return backward_into(ds, cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, dp, ws, rest, plan, plan_bytes, st, header);
+  const Route r = route_of(e.ds, nnz, B, offsets != nullptr, rowidx == nullptr && offsets != nullptr);
+  return backward_into(r, e.ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, dp, ws, rest, plan, plan_bytes, e.st, e.header);
 }
 
 static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state,
@@ -1122,40 +1057,28 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
                           const int32_t* nnz_dev, int64_t B, const float* d_output, float lr, float eps,
                           void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
                           void* stream) {
-  DevShape ds;
-  int rc = pending_device_fault();
+  Entry e;
+  int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
-  rc = make_dev_shape(shape, &ds);
-  if (rc) return rc;
-  rc = check_lookup_args(cores, indices, nnz, B);
-  if (rc) return rc;
+  const DevShape& ds = e.ds;
   if (nnz == 0) return TTEMB_OK;  // zero gradient: SGD is a no-op, Adagrad adds 0 and divides 0
   if (d_output == nullptr) return fail(TTEMB_E_BADARG, "d_output is null");
   const int64_t need = kFast3HeaderBytes + grad_scratch_bytes(ds);
   if (workspace == nullptr || workspace_bytes < need)
     return fail(TTEMB_E_WORKSPACE, "backward needs %lld workspace bytes, got %lld", (long long)need, (long long)workspace_bytes);
-  void* header = workspace;   // the grouped path's persistent words: the first kFast3HeaderBytes of every lookup workspace
-  workspace = reinterpret_cast<char*>(workspace) + kFast3HeaderBytes;
-  workspace_bytes -= kFast3HeaderBytes;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  CorePtrs cp;
-  CorePtrsMut gp;
-  char* ws = reinterpret_cast<char*>(workspace);
+  CorePtrsMut gp;   // the gradient scratch behind the header
   int64_t off = 0;
   for (int t = 0; t < TTEMB_MAX_CORES; ++t) {
-    cp.c[t] = t < ds.T ? cores[t] : nullptr;
-    gp.c[t] = nullptr;
-    if (t < ds.T) {
-      gp.c[t] = reinterpret_cast<float*>(ws + off);
-      off += align256((int64_t)ds.p[t] * ds.row_len[t] * 4);
-    }
+    gp.c[t] = t < ds.T ? reinterpret_cast<float*>(e.ws + off) : nullptr;
+    if (t < ds.T) off += align256((int64_t)ds.p[t] * ds.row_len[t] * 4);
   }
-  char* rest_ws = ws + off;
-  int64_t rest = workspace_bytes - off;
-  rc = resolve_rowidx(&rowidx, offsets, nnz, B, &rest_ws, &rest, st, use_fast3(ds, nnz, B, offsets != nullptr));
+  char* rest_ws = e.ws + off;
+  int64_t rest = e.ws_bytes - off;
+  rc = resolve_rowidx(rowidx, offsets, nnz, &rest_ws, &rest);
   if (rc) return rc;
+  const Route r = route_of(ds, nnz, B, offsets != nullptr, rowidx == nullptr && offsets != nullptr);
   // the grouped path of a one-piece call applies the step inside its last kernel; every other route writes gradients, then steps
-  const bool f3 = use_fast3(ds, nnz, B, offsets != nullptr) && one_piece(ds, nnz, B);
+  const bool fused = r.kind == kGrouped && fast3_fits(ds, nnz, B);
   bool aligned4 = true;
   FusedUpdate upd;
   memset(&upd, 0, sizeof(upd));
@@ -1167,11 +1090,9 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   if (!aligned4) return fail(TTEMB_E_BADARG, "null core / optimizer state");
   upd.lr = lr;
   upd.eps = eps;
-  // the grouped path applies the step inside its last kernel; the generic path writes gradients, then steps
-  bool grouped = false;
-  rc = backward_into(ds, cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, gp, rest_ws, rest, plan, plan_bytes, st,
-                     header, f3 ? &upd : nullptr, &grouped);
-  if (rc || f3) return rc;
+  rc = backward_into(r, ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, gp, rest_ws, rest, plan, plan_bytes, e.st,
+                     e.header, fused ? &upd : nullptr);
+  if (rc || fused) return rc;
   Seg3 seg;
   memset(&seg, 0, sizeof(seg));
   int64_t nmax = 0;
@@ -1187,9 +1108,10 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   if (!aligned) return fail(TTEMB_E_BADARG, "cores / optimizer state must be 16-byte aligned");
   int64_t blocks = (nmax / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
-  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, st, seg, lr, eps,
+  // (a grouped backward left its verdict in the header's poison word: a poisoned plan leaves the parameters alone)
+  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, e.st, seg, lr, eps,
                      opt_state ? 1 : 0,
-                     grouped ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(header) + kHeaderPoisonOffset) : nullptr);
+                     r.grouped ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(e.header) + kHeaderPoisonOffset) : nullptr);
   return check_hip(hipGetLastError(), "fused_step_kernel");
 }
 
@@ -1227,24 +1149,16 @@ int64_t ttemb_window_workspace_bytes(const ttemb_shape_t* shape, int32_t op, int
 }
 
 static int window_args(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices, const int64_t* offsets,
-                       int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, void** workspace, int64_t* workspace_bytes,
-                       DevShape* ds, CorePtrs* cp, void** header) {
-  int rc = pending_device_fault();
-  if (rc) return rc;
-  rc = make_dev_shape(shape, ds);
-  if (rc) return rc;
-  rc = check_lookup_args(cores, indices, nnz, B);
+                       int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, void* workspace, int64_t workspace_bytes,
+                       void* stream, Entry* e) {
+  int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, e);
   if (rc) return rc;
   if (offsets == nullptr) return fail(TTEMB_E_BADARG, "a window needs the bag boundaries (offsets)");
   if (bag0 < 0 || B < 0 || bag0 + B > bags_total) return fail(TTEMB_E_BADARG, "the window [%lld, %lld) does not lie inside the call's %lld bags",
                                                                 (long long)bag0, (long long)(bag0 + B), (long long)bags_total);
   if (current_path() == TTEMB_PATH_GENERIC || current_path() == TTEMB_PATH_PER_BAG)
     return fail(TTEMB_E_UNSUPPORTED, "a window is served by the grouped kernels (path forced elsewhere)");
-  for (int t = 0; t < TTEMB_MAX_CORES; ++t) cp->c[t] = t < ds->T ? cores[t] : nullptr;
-  if (*workspace == nullptr || *workspace_bytes < kFast3HeaderBytes) return fail(TTEMB_E_WORKSPACE, "a window call needs ttemb_window_workspace_bytes() bytes");
-  *header = *workspace;
-  *workspace = reinterpret_cast<char*>(*workspace) + kFast3HeaderBytes;
-  *workspace_bytes -= kFast3HeaderBytes;
+  if (e->header == nullptr) return fail(TTEMB_E_WORKSPACE, "a window call needs ttemb_window_workspace_bytes() bytes");
   return TTEMB_OK;
 }
 
@@ -1252,32 +1166,27 @@ int ttemb_forward_window(const ttemb_shape_t* shape, const float* const* cores, 
                          int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, float* output, void* workspace,
                          int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_forward_window");
-  DevShape ds;
-  CorePtrs cp;
-  void* header = nullptr;
-  int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, &workspace, &workspace_bytes, &ds, &cp, &header);
+  Entry e;
+  int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, workspace, workspace_bytes, stream, &e);
   if (rc || B == 0) return rc;
   if (output == nullptr) return fail(TTEMB_E_BADARG, "output is null");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (nnz == 0) return launch_zero(output + bag0 * ds.D, (size_t)B * ds.D * 4, st, "zero the window's rows");
-  return launch_forward_window_fast3(ds, cp, indices, offsets, nnz, bags_total, bag0, B, output, workspace, workspace_bytes, st, header);
+  if (nnz == 0) return launch_zero(output + bag0 * e.ds.D, (size_t)B * e.ds.D * 4, e.st, "zero the window's rows");
+  return launch_forward_window_fast3(e.ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, output, e.ws, e.ws_bytes, e.st, e.header);
 }
 
 static int backward_window(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, float* const* d_cores,
                            const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B,
                            const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream) {
-  DevShape ds;
-  CorePtrs cp;
-  void* header = nullptr;
-  int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, &workspace, &workspace_bytes, &ds, &cp, &header);
+  Entry e;
+  int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const DevShape& ds = e.ds;
   CorePtrsMut dp;
   for (int t = 0; t < TTEMB_MAX_CORES; ++t) dp.c[t] = (d_cores != nullptr && t < ds.T) ? d_cores[t] : nullptr;
   if (d_cores != nullptr) {   // dense: every gradient is written whole
     for (int t = 0; t < ds.T; ++t)
       if (d_cores[t] == nullptr) return fail(TTEMB_E_BADARG, "d_cores[%d] is null", t);
-    if (nnz == 0 || B == 0) return launch_zero_cores(ds, dp, st);
+    if (nnz == 0 || B == 0) return launch_zero_cores(ds, dp, e.st);
   } else if (nnz == 0 || B == 0) {
     return TTEMB_OK;   // zero gradient: SGD is a no-op, Adagrad adds 0 and divides 0
   }
@@ -1293,8 +1202,8 @@ static int backward_window(const ttemb_shape_t* shape, float* const* cores, floa
     upd.lr = lr;
     upd.eps = eps;
   }
-  return launch_backward_window_fast3(ds, cp, indices, offsets, nnz, bags_total, bag0, B, d_output, dp, workspace, workspace_bytes, st,
-                                      d_cores == nullptr ? &upd : nullptr, header);
+  return launch_backward_window_fast3(ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, d_output, dp, e.ws, e.ws_bytes, e.st,
+                                      d_cores == nullptr ? &upd : nullptr, e.header);
 }
 
 int ttemb_backward_dense_window(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices, const int64_t* offsets,

@@ -3739,65 +3739,6 @@ static int run_backward_wide(const DevShape& s, const CorePtrs& cores, const Gro
   return check_hip(hipGetLastError(), "fast3_finalize_kernel (wide)");
 }
 
-int launch_forward_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices,
-                         const int64_t* rowidx, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
-                         int64_t B, float* output, bool zero_rows, void* ws, int64_t ws_bytes, void* plan_buf,
-                         int64_t plan_bytes, int phase, hipStream_t st, void* header) {
-  if (nnz <= 0) return TTEMB_OK;
-  if (!fits_piece(s, nnz, B)) {
-    // The call is cut into pieces (struct Piece).  The id-only half of a two-phase forward does nothing then, the lookup half
-    // is the whole forward; the caller's plan buffer is not used (a plan describes one piece; the backward regroups).
-    if (phase == 1) return TTEMB_OK;
-    if (offsets == nullptr) return fail(TTEMB_E_UNSUPPORTED, "a call of this size needs the bag boundaries (offsets)");
-    const int slots = piece_slots(s, nnz, B);
-    const int64_t head = pieces_head_bytes(s, nnz, B), li = piece_ids(s), np = nnz < li ? nnz : li;
-    if (ws == nullptr || ws_bytes < head) return fail(TTEMB_E_WORKSPACE, "forward needs room for the piece table");
-    Piece* tab = reinterpret_cast<Piece*>(ws);
-    hipLaunchKernelGGL(plan_pieces_kernel, dim3(1), dim3(64), 0, st, offsets, B, nnz, nnz_dev, (long long)li, (long long)piece_rows(s),
-                       s.D, slots, tab);
-    int rc = check_hip(hipGetLastError(), "plan_pieces_kernel");
-    for (int k = 0; k < slots && rc == TTEMB_OK; ++k) {
-      GroupPlan plan;
-      rc = prepare(s, cores, false, indices, rowidx, offsets, np, nullptr, B, zero_rows ? output : nullptr,
-                   reinterpret_cast<char*>(ws) + head, ws_bytes - head, nullptr, 0, 0, &plan, st, header, tab + k);
-      if (rc) break;
-      rc = fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-      if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_forward_direct<a, b, c, d, e>(s, cores, plan, np, piece_rows(s), output, st);
-        TTEMB_WIDE3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-      } else {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_forward<a, b, c, d, e>(s, cores, plan, np, piece_rows(s), output, st);
-        TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-      }
-    }
-    return rc;
-  }
-  GroupPlan plan;
-  // a whole forward (phase 0) on a frontier with few ids per group: the chain kernel forms the prefix products itself
-  const bool pfuse = (phase == 0 && pfuse_pays(s, nnz)) || (phase == 2 && pfuse_pays_after_grouping(s, nnz));
-  int rc = prepare(s, cores, false, indices, rowidx, offsets, nnz, nnz_dev, B, zero_rows ? output : nullptr, ws, ws_bytes,
-                   plan_buf, plan_bytes, phase, &plan, st, header, nullptr, pfuse);   // phase 0 / 1 / 2 = whole forward / ids only / lookup on a grouped plan
-  if (rc || phase == 1) return rc;
-  if (pfuse) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward_pfuse<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
-    TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward_direct<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
-    TTEMB_WIDE3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  if (classify(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
-    TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-}
-
 // The backward chunk kernel that also forms the per-group products (GF): shapes with at least two groups per MFMA tile and
 // q1 r2 a multiple of 16 (the K permutation of its dG0 product moves 16-byte pieces).  Taken by frontiers with few ids per
 // group (the rule of the forward that forms its own prefix products) whose dG2 reduction is not fused into the chunk kernel.
@@ -3940,74 +3881,6 @@ static int run_backward(const DevShape& s, const CorePtrs& cores, const GroupPla
   return check_hip(hipGetLastError(), "fast3_finalize_kernel");
 }
 
-int launch_backward_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices,
-                          const int64_t* rowidx, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
-                          int64_t B, const float* d_output, const CorePtrsMut& d_cores, void* ws, int64_t ws_bytes,
-                          const void* plan_buf, int64_t plan_bytes, hipStream_t st, const FusedUpdate* update, void* header) {
-  FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  if (update != nullptr) upd = *update;
-  upd.poison_out = header != nullptr ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(header) + kHeaderPoisonOffset) : nullptr;
-  upd.sticky = 0;
-  static_assert(kHeaderPoisonOffset == 16 + (int64_t)kCountBanks * kMaxRanges * 8, "the poison word sits behind the range counters");
-  // every core gradient is written whole by the finalize kernel (an empty call in a fused mode is a no-op)
-  for (int t = 0; t < s.T; ++t) {
-    if (nnz > 0 || update != nullptr) continue;
-    int rc = launch_zero(d_cores.c[t], (size_t)s.p[t] * s.row_len[t] * 4, st, "zero d_core");
-    if (rc) return rc;
-  }
-  if (nnz <= 0) return TTEMB_OK;
-  if (!fits_piece(s, nnz, B)) {
-    // piece by piece (struct Piece): every piece regroups its ids (a plan describes one piece) and ADDS its gradient to what
-    // the pieces before it left -- the reference accumulates its batch_count chunks into d_tt_cores the same way and steps
-    // once (tt_embeddings_cuda.cu:633-651).  The optimiser step is the caller's, on the summed gradient.
-    if (update != nullptr) return fail(TTEMB_E_BADARG, "internal: a call in pieces writes gradients, the step follows");
-    if (offsets == nullptr) return fail(TTEMB_E_UNSUPPORTED, "a call of this size needs the bag boundaries (offsets)");
-    const int slots = piece_slots(s, nnz, B);
-    const int64_t head = pieces_head_bytes(s, nnz, B), li = piece_ids(s), np = nnz < li ? nnz : li;
-    if (ws == nullptr || ws_bytes < head) return fail(TTEMB_E_WORKSPACE, "backward needs room for the piece table");
-    Piece* tab = reinterpret_cast<Piece*>(ws);
-    hipLaunchKernelGGL(plan_pieces_kernel, dim3(1), dim3(64), 0, st, offsets, B, nnz, nnz_dev, (long long)li, (long long)piece_rows(s),
-                       s.D, slots, tab);
-    int rc = check_hip(hipGetLastError(), "plan_pieces_kernel");
-    for (int k = 0; k < slots && rc == TTEMB_OK; ++k) {
-      GroupPlan plan;
-      rc = prepare(s, cores, true, indices, rowidx, offsets, np, nullptr, B, nullptr, reinterpret_cast<char*>(ws) + head, ws_bytes - head,
-                   nullptr, 0, 0, &plan, st, header, tab + k);
-      if (rc) break;
-      upd.eps = k > 0 ? 1.f : 0.f;   // (dense mode: finalize adds to the gradient instead of writing it)
-      upd.sticky = k > 0 ? 1 : 0;    // (a poisoned piece marks the whole call)
-      rc = fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-      if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_backward_wide<a, b, c, d, e>(s, cores, plan, np, piece_rows(s), d_output, d_cores, upd, st);
-        TTEMB_WIDE3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-      } else {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_backward<a, b, c, d, e>(s, cores, plan, np, piece_rows(s), d_output, d_cores, upd, st);
-        TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-      }
-    }
-    return rc;
-  }
-  GroupPlan plan;
-  int rc = prepare(s, cores, true, indices, rowidx, offsets, nnz, nnz_dev, B, nullptr, ws, ws_bytes,
-                   const_cast<void*>(plan_buf), plan_bytes,
-                   plan_buf != nullptr && plan_bytes >= fast3_plan_bytes(s, nnz) ? 3 : 0, &plan, st, header);
-  if (rc) return rc;
-  if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_backward_wide<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
-    TTEMB_WIDE3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  if (classify(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_backward<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
-    TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-}
-
 // ---------------------------------------------------------------------------------
 // A WINDOW of a longer id list: the bags [bag0, bag0 + B) of `offsets` and the ids that belong to them -- one table of a
 // table-batched call (the reference passes `tableidx` to its kernels and never learns on the host where a table's ids begin,
@@ -4036,30 +3909,169 @@ int64_t fast3_window_workspace_bytes(const DevShape& s, bool bwd, int64_t nnz) {
   return kWindowHeadBytes + carve_workspace(s, nnz, bwd, true, true, nullptr, nullptr) + 256;
 }
 
-int launch_forward_window_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices, const int64_t* offsets,
-                                int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, float* output, void* ws, int64_t ws_bytes,
-                                hipStream_t st, void* header) {
-  if (!fast3_window_fits(s, nnz, bags_total, B)) return fail(TTEMB_E_UNSUPPORTED, "the grouped kernels do not cover this window (shape or size)");
-  if (ws == nullptr || ws_bytes < kWindowHeadBytes) return fail(TTEMB_E_WORKSPACE, "forward needs room for the window");
-  Piece* tab = reinterpret_cast<Piece*>(ws);
-  hipLaunchKernelGGL(window_piece_kernel, dim3(1), dim3(64), 0, st, offsets, (long long)bag0, (long long)B, s.D, tab);
-  int rc = check_hip(hipGetLastError(), "window_piece_kernel");
-  if (rc) return rc;
-  GroupPlan plan;
-  rc = prepare(s, cores, false, indices, nullptr, offsets, nnz, nullptr, bags_total, output, reinterpret_cast<char*>(ws) + kWindowHeadBytes,
-               ws_bytes - kWindowHeadBytes, nullptr, 0, 0, &plan, st, header, tab);
-  if (rc) return rc;
-  rc = fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
+// ---------------------------------------------------------------------------------
+// The grouped calls: a prepared plan through the chain kernels, once for a call that fits one piece, piece by piece for one
+// that does not, and as a one-slot piece table for a window.
+// ---------------------------------------------------------------------------------
+// the forward chain on a prepared plan: the chain kernel that forms the prefix products itself (pfuse), the chain kernel on the
+// plan's products, or the wide ranks' direct forward; `B` bags from the plan's row base are the rows it addresses
+static int forward_plan(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int64_t B, float* output,
+                        bool pfuse, hipStream_t st) {
+  // (the order of the dispatches is the order the kernel templates are instantiated in, and so of the code object's kernels)
   if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_forward_direct<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward_direct<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
     TTEMB_WIDE3_SHAPES(TTEMB_X)
 #undef TTEMB_X
-  } else {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_forward<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
+  }
+  if (classify(s) && !pfuse) {
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
     TTEMB_FAST3_SHAPES(TTEMB_X)
 #undef TTEMB_X
   }
+  if (classify(s)) {
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_forward_pfuse<a, b, c, d, e>(s, cores, plan, nnz, B, output, st);
+    TTEMB_FAST3_SHAPES(TTEMB_X)
+#undef TTEMB_X
+  }
+  return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
+}
+
+// the backward chain on a prepared plan
+static int backward_plan(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int64_t B,
+                         const float* d_output, const CorePtrsMut& d_cores, const FusedUpdate& upd, hipStream_t st) {
+  if (wide(s)) {
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_backward_wide<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
+    TTEMB_WIDE3_SHAPES(TTEMB_X)
+#undef TTEMB_X
+  }
+  if (classify(s)) {
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_backward<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
+    TTEMB_FAST3_SHAPES(TTEMB_X)
+#undef TTEMB_X
+  }
+  return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
+}
+
+// the step a backward applies (none: `update` is null, the gradient is written -- eps = 0 then, not added to an earlier piece's)
+// and where its finalize kernel leaves the poison verdict
+static FusedUpdate chain_update(const FusedUpdate* update, void* header) {
+  static_assert(kHeaderPoisonOffset == 16 + (int64_t)kCountBanks * kMaxRanges * 8, "the poison word sits behind the range counters");
+  FusedUpdate upd;
+  memset(&upd, 0, sizeof(upd));
+  if (update != nullptr) upd = *update;
+  upd.poison_out = header != nullptr ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(header) + kHeaderPoisonOffset) : nullptr;
+  upd.sticky = 0;
+  return upd;
+}
+
+// A call past one piece: the piece table at the head of the workspace, filled on the device (plan_pieces_kernel); *head: its bytes
+static int plan_pieces(const DevShape& s, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, void* ws,
+                       int64_t ws_bytes, const char* what, hipStream_t st, int* slots, int64_t* head) {
+  if (offsets == nullptr) return fail(TTEMB_E_UNSUPPORTED, "a call of this size needs the bag boundaries (offsets)");
+  *slots = piece_slots(s, nnz, B);
+  *head = pieces_head_bytes(s, nnz, B);
+  if (ws == nullptr || ws_bytes < *head) return fail(TTEMB_E_WORKSPACE, "%s needs room for the piece table", what);
+  hipLaunchKernelGGL(plan_pieces_kernel, dim3(1), dim3(64), 0, st, offsets, B, nnz, nnz_dev, (long long)piece_ids(s), (long long)piece_rows(s),
+                     s.D, *slots, reinterpret_cast<Piece*>(ws));
+  return check_hip(hipGetLastError(), "plan_pieces_kernel");
+}
+
+// A window: a one-slot piece table at the head of the workspace, filled on the device (window_piece_kernel)
+static int plan_window(const DevShape& s, const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, void* ws,
+                       int64_t ws_bytes, const char* what, hipStream_t st) {
+  if (!fast3_window_fits(s, nnz, bags_total, B)) return fail(TTEMB_E_UNSUPPORTED, "the grouped kernels do not cover this window (shape or size)");
+  if (ws == nullptr || ws_bytes < kWindowHeadBytes) return fail(TTEMB_E_WORKSPACE, "%s needs room for the window", what);
+  hipLaunchKernelGGL(window_piece_kernel, dim3(1), dim3(64), 0, st, offsets, (long long)bag0, (long long)B, s.D, reinterpret_cast<Piece*>(ws));
+  return check_hip(hipGetLastError(), "window_piece_kernel");
+}
+
+// The `slots` pieces of the table at `ws` one after the other, each on the tables behind `head` bytes: every piece regroups its
+// (at most `ids`) ids -- a plan describes one piece --, then run(plan, k) takes piece k through the chain
+template <class Run>
+static int run_pieces(const DevShape& s, const CorePtrs& cores, bool bwd, const int64_t* indices, const int64_t* rowidx,
+                      const int64_t* offsets, int64_t ids, int64_t bags, float* zero_out, int slots, void* ws, int64_t head,
+                      int64_t ws_bytes, hipStream_t st, void* header, Run run) {
+  const Piece* tab = reinterpret_cast<const Piece*>(ws);
+  int rc = TTEMB_OK;
+  for (int k = 0; k < slots && rc == TTEMB_OK; ++k) {
+    GroupPlan plan;
+    rc = prepare(s, cores, bwd, indices, rowidx, offsets, ids, nullptr, bags, zero_out, reinterpret_cast<char*>(ws) + head,
+                 ws_bytes - head, nullptr, 0, 0, &plan, st, header, tab + k);
+    if (rc == TTEMB_OK) rc = run(plan, k);
+  }
   return rc;
+}
+
+int launch_forward_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices,
+                         const int64_t* rowidx, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
+                         int64_t B, float* output, bool zero_rows, void* ws, int64_t ws_bytes, void* plan_buf,
+                         int64_t plan_bytes, int phase, hipStream_t st, void* header) {
+  if (nnz <= 0) return TTEMB_OK;
+  float* zero_out = zero_rows ? output : nullptr;
+  if (!fits_piece(s, nnz, B)) {
+    // The call is cut into pieces (struct Piece).  The id-only half of a two-phase forward does nothing then, the lookup half
+    // is the whole forward; the caller's plan buffer is not used (a plan describes one piece; the backward regroups).
+    if (phase == 1) return TTEMB_OK;
+    int slots = 0;
+    int64_t head = 0;
+    int rc = plan_pieces(s, offsets, nnz, nnz_dev, B, ws, ws_bytes, "forward", st, &slots, &head);
+    if (rc) return rc;
+    const int64_t li = piece_ids(s), np = nnz < li ? nnz : li;
+    return run_pieces(s, cores, false, indices, rowidx, offsets, np, B, zero_out, slots, ws, head, ws_bytes, st, header,
+                      [&](const GroupPlan& plan, int) { return forward_plan(s, cores, plan, np, piece_rows(s), output, false, st); });
+  }
+  GroupPlan plan;
+  // a whole forward (phase 0) on a frontier with few ids per group: the chain kernel forms the prefix products itself
+  const bool pfuse = (phase == 0 && pfuse_pays(s, nnz)) || (phase == 2 && pfuse_pays_after_grouping(s, nnz));
+  int rc = prepare(s, cores, false, indices, rowidx, offsets, nnz, nnz_dev, B, zero_out, ws, ws_bytes,
+                   plan_buf, plan_bytes, phase, &plan, st, header, nullptr, pfuse);   // phase 0 / 1 / 2 = whole forward / ids only / lookup on a grouped plan
+  if (rc || phase == 1) return rc;
+  return forward_plan(s, cores, plan, nnz, B, output, pfuse, st);
+}
+
+int launch_backward_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices,
+                          const int64_t* rowidx, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
+                          int64_t B, const float* d_output, const CorePtrsMut& d_cores, void* ws, int64_t ws_bytes,
+                          const void* plan_buf, int64_t plan_bytes, hipStream_t st, const FusedUpdate* update, void* header) {
+  FusedUpdate upd = chain_update(update, header);
+  // every core gradient is written whole by the finalize kernel (an empty call in a fused mode is a no-op)
+  for (int t = 0; t < s.T && nnz <= 0 && update == nullptr; ++t) {
+    int rc = launch_zero(d_cores.c[t], (size_t)s.p[t] * s.row_len[t] * 4, st, "zero d_core");
+    if (rc) return rc;
+  }
+  if (nnz <= 0) return TTEMB_OK;
+  if (!fits_piece(s, nnz, B)) {
+    // piece by piece: every piece ADDS its gradient to what the pieces before it left -- the reference accumulates its
+    // batch_count chunks into d_tt_cores the same way and steps once (tt_embeddings_cuda.cu:633-651).  The optimiser step is
+    // the caller's, on the summed gradient.
+    if (update != nullptr) return fail(TTEMB_E_BADARG, "internal: a call in pieces writes gradients, the step follows");
+    int slots = 0;
+    int64_t head = 0;
+    int rc = plan_pieces(s, offsets, nnz, nnz_dev, B, ws, ws_bytes, "backward", st, &slots, &head);
+    if (rc) return rc;
+    const int64_t li = piece_ids(s), np = nnz < li ? nnz : li;
+    return run_pieces(s, cores, true, indices, rowidx, offsets, np, B, nullptr, slots, ws, head, ws_bytes, st, header,
+                      [&](const GroupPlan& plan, int k) {
+                        upd.eps = k > 0 ? 1.f : 0.f;   // (dense mode: finalize adds to the gradient instead of writing it)
+                        upd.sticky = k > 0 ? 1 : 0;    // (a poisoned piece marks the whole call)
+                        return backward_plan(s, cores, plan, np, piece_rows(s), d_output, d_cores, upd, st);
+                      });
+  }
+  GroupPlan plan;
+  int rc = prepare(s, cores, true, indices, rowidx, offsets, nnz, nnz_dev, B, nullptr, ws, ws_bytes,
+                   const_cast<void*>(plan_buf), plan_bytes,
+                   plan_buf != nullptr && plan_bytes >= fast3_plan_bytes(s, nnz) ? 3 : 0, &plan, st, header);
+  if (rc) return rc;
+  return backward_plan(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
+}
+
+int launch_forward_window_fast3(const DevShape& s, const CorePtrs& cores, const int64_t* indices, const int64_t* offsets,
+                                int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, float* output, void* ws, int64_t ws_bytes,
+                                hipStream_t st, void* header) {
+  const int rc = plan_window(s, offsets, nnz, bags_total, bag0, B, ws, ws_bytes, "forward", st);
+  if (rc) return rc;
+  return run_pieces(s, cores, false, indices, nullptr, offsets, nnz, bags_total, output, 1, ws, kWindowHeadBytes, ws_bytes, st, header,
+                    [&](const GroupPlan& plan, int) { return forward_plan(s, cores, plan, nnz, B, output, false, st); });
 }
 
 // `update` != null: the optimiser step of THIS table rides in the finalize kernel (a window is a whole table's share of the
@@ -4068,33 +4080,11 @@ int launch_backward_window_fast3(const DevShape& s, const CorePtrs& cores, const
                                  int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, const float* d_output,
                                  const CorePtrsMut& d_cores, void* ws, int64_t ws_bytes, hipStream_t st, const FusedUpdate* update,
                                  void* header) {
-  if (!fast3_window_fits(s, nnz, bags_total, B)) return fail(TTEMB_E_UNSUPPORTED, "the grouped kernels do not cover this window (shape or size)");
-  if (ws == nullptr || ws_bytes < kWindowHeadBytes) return fail(TTEMB_E_WORKSPACE, "backward needs room for the window");
-  FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  if (update != nullptr) upd = *update;
-  upd.poison_out = header != nullptr ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(header) + kHeaderPoisonOffset) : nullptr;
-  upd.sticky = 0;
-  if (update == nullptr) upd.eps = 0.f;   // (dense mode: the gradient is written, not added to an earlier piece's)
-  Piece* tab = reinterpret_cast<Piece*>(ws);
-  hipLaunchKernelGGL(window_piece_kernel, dim3(1), dim3(64), 0, st, offsets, (long long)bag0, (long long)B, s.D, tab);
-  int rc = check_hip(hipGetLastError(), "window_piece_kernel");
+  const int rc = plan_window(s, offsets, nnz, bags_total, bag0, B, ws, ws_bytes, "backward", st);
   if (rc) return rc;
-  GroupPlan plan;
-  rc = prepare(s, cores, true, indices, nullptr, offsets, nnz, nullptr, bags_total, nullptr, reinterpret_cast<char*>(ws) + kWindowHeadBytes,
-               ws_bytes - kWindowHeadBytes, nullptr, 0, 0, &plan, st, header, tab);
-  if (rc) return rc;
-  rc = fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
-  if (wide(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_backward_wide<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
-    TTEMB_WIDE3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  } else {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) rc = run_backward<a, b, c, d, e>(s, cores, plan, nnz, B, d_output, d_cores, upd, st);
-    TTEMB_FAST3_SHAPES(TTEMB_X)
-#undef TTEMB_X
-  }
-  return rc;
+  const FusedUpdate upd = chain_update(update, header);
+  return run_pieces(s, cores, true, indices, nullptr, offsets, nnz, bags_total, nullptr, 1, ws, kWindowHeadBytes, ws_bytes, st, header,
+                    [&](const GroupPlan& plan, int) { return backward_plan(s, cores, plan, nnz, B, d_output, d_cores, upd, st); });
 }
 
 #include "ttemb_small3.inc"

@@ -128,6 +128,26 @@ def test_size_queries_over_every_shape_and_size():
                     assert nat.kernel_family(shape, nnz, B, True) >= 0 and nat.kernel_family(shape, nnz, B, False) >= 0
 
 
+def test_route_table_is_pinned(tmp_path):
+    """Every size query of tests/golden/make_route_table.py's sweep (forced path x shape x size x piece limits: workspace for the
+    four ops, plan, kernel family with and without offsets, window workspace) answers what route_table.npz recorded.  The sweep
+    runs in a child process with no device visible, where the library sizes for 256 CUs as the table was taken."""
+    import subprocess
+    import sys
+    out = tmp_path / "routes.npz"
+    code = (f"import sys; sys.path.insert(0, {os.path.join(ROOT, 'tests', 'golden')!r}); import numpy as np, torch; "
+            "assert torch.cuda.device_count() == 0, 'the device is not hidden'; "
+            "import make_route_table as m; np.savez(sys.argv[1], **m.sweep())")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
+    r = subprocess.run([sys.executable, "-c", code, str(out)], env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got, want = np.load(out), load_golden("route_table")
+    assert np.array_equal(got["key"], want["key"])
+    bad = np.argwhere(got["value"] != want["value"])
+    assert len(bad) == 0, [(want["key"][i].tolist(), str(want["columns"][j]), int(want["value"][i, j]), int(got["value"][i, j]))
+                           for i, j in bad[:10]]
+
+
 def test_window_size_query_is_host_arithmetic():
     """ttemb_window_workspace_bytes: what a window call (one table of a table-batched call) needs, -1 through the binding when
     the grouped kernels do not serve the window -- the caller then splits the id list on the host."""
