@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import logging
 import math
+import warnings
 from enum import Enum, unique
 from typing import List, Optional, Sequence
 
@@ -36,7 +37,8 @@ _LOG = logging.getLogger(__name__)
 class OptimType(Enum):
     """Optimiser selector; value strings match the reference (tt_embeddings_ops.py:18-33).
     SGD / EXACT_SGD run the fused in-backward SGD; everything else runs fused Adagrad,
-    exactly as the reference dispatches (:229-286)."""
+    exactly as the reference dispatches (:229-286).  EXACT_SGD also turns on exact mode, the reference's documented
+    meaning ("deterministic updates (via sorting + segment reduction)", :20-23): see ``_ExactLookup``."""
     SGD = "sgd"
     EXACT_SGD = "exact_sgd"
     LAMB = "lamb"
@@ -407,6 +409,59 @@ class _BucketLookup(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _ExactLookup(torch.autograd.Function):
+    """Exact mode: one table's lookup on the bit-reproducible kernels (``ttemb_forward_exact`` / ``ttemb_backward_*_exact``,
+    include/ttemb.h "Exact mode").  Outputs, gradients, updated cores and optimizer state are a function of the inputs
+    only.  Fused SGD / Adagrad (``sparse``) update the touched rows only; dense gradients go to autograd, or into the
+    ``_dense_grad_out`` bucket of ``ttemb_dist.TTDataParallel`` (adding to it after the first backward of a step, like the
+    plain lookup).  A module with several tables runs one exact call per table on the host-split id list."""
+
+    @staticmethod
+    def forward(ctx, module: "TableBatchedTTEmbeddingBag", table: int, B: int, indices: torch.Tensor,
+                offsets: torch.Tensor, *tt_cores: torch.Tensor) -> torch.Tensor:
+        ctx.module, ctx.table, ctx.B, ctx.indices, ctx.offsets = module, table, B, indices, offsets
+        if module._before_weights is not None:
+            module._before_weights()   # a data-parallel update of the cores is pending: finish it first
+        out = torch.empty((B, module.embedding_dim), dtype=torch.float32, device=indices.device)
+        _nat.forward_exact(module._shape, _nat.core_ptrs(tt_cores, table), indices, offsets, B, out, module._ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        m, table, B, indices, offsets = ctx.module, ctx.table, ctx.B, ctx.indices, ctx.offsets
+        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
+            d_output = d_output.contiguous().float()
+        cores = _nat.core_ptrs(m.tt_cores, table)
+        n_fixed = 5
+        if m.sparse:
+            state = None if m.optimizer in _SGD_LIKE else _nat.core_ptrs(list(m.optimizer_state), table)
+            _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, opt_state=state,
+                                lr=float(m.learning_rate), eps=float(m.eps))
+            return (None,) * (n_fixed + len(m.tt_cores))
+        m._last_bwd_grouped = False   # no bounded device-side waits: nothing in the workspace header to look at
+        bucket = getattr(m, "_dense_grad_out", None)
+        if bucket is not None and m.num_tables == 1:
+            if m._bucket_filled:   # a second backward before dp.step(): to scratch, then added (what AccumulateGrad does)
+                more = [torch.empty_like(b) for b in bucket]
+                _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=more)
+                torch._foreach_add_(bucket, more)
+            else:
+                _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=bucket)
+                m._bucket_filled = True
+            return (None,) * (n_fixed + len(m.tt_cores))
+        grads = [torch.empty_like(c[table] if c.dim() == 3 else c) for c in m.tt_cores]
+        _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=grads)
+        full = []
+        for t, g in enumerate(grads):
+            if m.num_tables == 1:
+                full.append(g.unsqueeze(0))
+            else:  # only this table's slice of the [num_tables, p, row] parameter gets gradient
+                z = torch.zeros_like(m.tt_cores[t].data)
+                z[table] = g
+                full.append(z)
+        return (None,) * n_fixed + tuple(full)
+
+
 class _ReplayLookup(torch.autograd.Function):
     """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each."""
 
@@ -446,18 +501,35 @@ class CapturedLookup:
         cores = module._cores()
         state = None if module.optimizer in _SGD_LIKE else module._states()
         lr, eps = float(module.learning_rate), float(module.eps)
+        self.exact = module._exact_active()   # exact mode: the graphs hold the exact kernels
+        if self.exact:
+            self.plan = None
+
+            def fwd():
+                _nat.forward_exact(module._shape, _nat.core_ptrs(cores), self.indices, self.offsets, self.B, self.output,
+                                   self._lean.ws)
+
+            def bwd():
+                _nat.backward_exact(module._shape, _nat.core_ptrs(cores), self.indices, self.offsets, self.B, self.d_output,
+                                    self._lean.ws, opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps)
+        else:
+            def fwd():
+                self.plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output)
+
+            def bwd():
+                self._lean.backward(cores, state, self.indices, self.offsets, self.nnz, self.B, self.d_output, lr, eps, self.plan)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):   # warm-up outside capture: workspace allocation, LDS-size attributes, size queries
-            plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output)
+            fwd()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         _nat.init()   # the pinned fault word exists before anything is captured (a capture must not allocate it)
         self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.fwd_graph):
-            self.plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output)
+            fwd()
         with torch.cuda.graph(self.bwd_graph):   # (a zero gradient: the captured update leaves the cores as they are)
-            self._lean.backward(cores, state, self.indices, self.offsets, self.nnz, self.B, self.d_output, lr, eps, self.plan)
+            bwd()
         self._lr, self._eps = lr, eps
         self._baked = self._pointers()
 
@@ -506,8 +578,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000) -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None) -> None:
         super().__init__()
+        # exact mode (``_ExactLookup``): True / False, or None = on for OptimType.EXACT_SGD and whenever
+        # torch.are_deterministic_algorithms_enabled() at call time
+        self.deterministic = deterministic
         assert num_tables > 0 and num_embeddings > 0 and embedding_dim > 0
         assert num_tables == 1 or not use_cache, "cannot use cache when num_tables != 1"
         T = len(tt_ranks) + 1
@@ -658,9 +733,35 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             sl = self._state_list = tuple(self.optimizer_state)
         return sl
 
-    def _lookup_one_table(self, table: int, B: int, indices: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    def _exact_requested(self) -> bool:
+        if self.deterministic is not None:
+            return bool(self.deterministic)
+        return self.optimizer == OptimType.EXACT_SGD or torch.are_deterministic_algorithms_enabled()
+
+    def _exact_active(self) -> bool:
+        """Whether this call runs in exact mode.  A request the exact kernels cannot serve (a shape outside their domain, a
+        live row cache) raises ``RuntimeError`` -- or, under ``torch.use_deterministic_algorithms(True, warn_only=True)``,
+        warns and runs the plain lookup."""
+        if not self._exact_requested():
+            return False
+        reason = getattr(self, "_exact_reason", False)
+        if reason is False:
+            reason = self._exact_reason = _nat.exact_unsupported_reason(self._shape)
+        if reason is None and self.use_cache and not self.warmup:
+            reason = "a live row cache (after cache_populate()) is not covered by exact mode"
+        if reason is None:
+            return True
+        if torch.is_deterministic_algorithms_warn_only_enabled():
+            warnings.warn(f"TTEmbeddingBag: exact mode unavailable, running the plain lookup: {reason}")
+            return False
+        raise RuntimeError(f"TTEmbeddingBag: exact mode was requested but is unavailable: {reason}")
+
+    def _lookup_one_table(self, table: int, B: int, indices: torch.Tensor, offsets: torch.Tensor,
+                          exact: Optional[bool] = None) -> torch.Tensor:
         nnz = indices.numel()
         dev = indices.device
+        if exact if exact is not None else self._exact_active():
+            return _ExactLookup.apply(self, table, B, indices, offsets, *self.tt_cores)
         live = self.use_cache and not self.warmup
         if not live:  # rows are derived from `offsets` inside the native calls: no separate launch, no tensor
             if self.num_tables == 1 and self._use_lean and not torch.is_grad_enabled():
@@ -703,12 +804,13 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         B = (offsets.numel() - 1) // self.num_tables
         if not self._fused_probe():
             self.update_cache(indices)
+        exact = self._exact_active()
         if self.num_tables == 1:
-            return self._lookup_one_table(0, B, indices, offsets).unsqueeze(0)
+            return self._lookup_one_table(0, B, indices, offsets, exact).unsqueeze(0)
         # every table is a window of the id list, its bounds read from `offsets` on the device (no host synchronisation) -- when the
         # grouped kernels serve the shape; else the id list is split on the host, one plain lookup per table
         nnz = indices.numel()
-        if (not self.use_cache and self._use_windows and nnz > 0 and B > 0
+        if (not exact and not self.use_cache and self._use_windows and nnz > 0 and B > 0
                 and _nat.window_workspace_bytes(self._shape, _nat.OP_BACKWARD, nnz, offsets.numel() - 1, B) >= 0):
             return _TablesLookup.apply(self, B, indices, offsets, *self.tt_cores)
         bounds = offsets[:: B].tolist()  # host sync: only this fallback of the multi-table path pays it
@@ -716,7 +818,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         for k in range(self.num_tables):
             lo, hi = int(bounds[k]), int(bounds[k + 1])
             offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
-            outs.append(self._lookup_one_table(k, B, indices[lo:hi].contiguous(), offs_k))
+            outs.append(self._lookup_one_table(k, B, indices[lo:hi].contiguous(), offs_k, exact))
         return torch.stack(outs, 0)
 
 
@@ -729,10 +831,10 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = True, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000) -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
-                         enforce_embedding_dim, batch_count)
+                         enforce_embedding_dim, batch_count, deterministic=deterministic)
 
     def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True) -> torch.Tensor:
         # same result as the reference's ``super().forward(...)[0]`` (:960-965) without the

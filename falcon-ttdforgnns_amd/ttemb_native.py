@@ -34,6 +34,8 @@ EXPORTED_SYMBOLS = (
     "ttemb_sgd_step", "ttemb_sgd_step_guarded", "ttemb_adagrad_step", "ttemb_cache_update", "ttemb_cache_update_one_sweep", "ttemb_cache_populate",
     "ttemb_preprocess", "ttemb_preprocess_update", "ttemb_cache_forward", "ttemb_cache_backward_sgd",
     "ttemb_cache_backward_dense", "ttemb_cache_backward_rowwise_adagrad",
+    "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_set_exact_grid", "ttemb_forward_exact",
+    "ttemb_backward_dense_exact", "ttemb_backward_sgd_exact", "ttemb_backward_adagrad_exact",
 )
 
 
@@ -110,9 +112,19 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_cache_backward_sgd.argtypes = [vp, vp, i64, vp, i64, vp, i64, f32, vp, vp, vp]
     lib.ttemb_cache_backward_dense.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp]
     lib.ttemb_cache_backward_rowwise_adagrad.argtypes = [vp, vp, i64, vp, i64, vp, i64, f32, f32, vp, vp, vp]
+    lib.ttemb_exact_workspace_bytes.restype = i64
+    lib.ttemb_exact_workspace_bytes.argtypes = [shp, i64, i64]
+    lib.ttemb_exact_plan_bytes.restype = i64
+    lib.ttemb_exact_plan_bytes.argtypes = [shp, i64]
+    lib.ttemb_set_exact_grid.argtypes = [i32]
+    lib.ttemb_forward_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, vp, i64, vp, i64, vp]
+    lib.ttemb_backward_dense_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, i64, vp]
+    lib.ttemb_backward_sgd_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, f32, vp, i64, vp, i64, vp]
+    lib.ttemb_backward_adagrad_exact.argtypes = [shp, vp, vp, vp, vp, i64, i64, vp, f32, f32, vp, i64, vp, i64, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
-        if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes"):
+        if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
+                        "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -440,6 +452,64 @@ def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.
             _check(LIB.ttemb_backward_sgd_window(*head, *ids, lr, _ptr(w), w.numel(), _stream(d_output)))
         else:
             _check(LIB.ttemb_backward_adagrad_window(*head, _ptr_array(opt_state), *ids, lr, eps, _ptr(w), w.numel(), _stream(d_output)))
+
+
+def exact_workspace_bytes(shape: Shape, nnz: int, B: int) -> int:
+    """Bytes the exact calls need (one workspace serves the forward and every backward), or -1 when the exact kernels do
+    not cover the shape (``exact_unsupported_reason`` says why)."""
+    key = ("exact", _shape_key(shape), nnz, B)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_exact_workspace_bytes(ctypes.byref(shape), nnz, B))
+        if n < 0 and n != E_UNSUPPORTED:
+            _check(n)
+        n = _size_cache[key] = (-1 if n < 0 else n)
+    return n
+
+
+def exact_unsupported_reason(shape: Shape) -> Optional[str]:
+    """None when the exact kernels cover the shape, else the library's reason."""
+    n = int(LIB.ttemb_exact_workspace_bytes(ctypes.byref(shape), 0, 0))
+    if n >= 0:
+        return None
+    if n != E_UNSUPPORTED:
+        _check(n)
+    return LIB.ttemb_last_error().decode()
+
+
+def set_exact_grid(workgroups: int = 0) -> None:
+    """Diagnostic: cap the grid of the exact kernels (0 = default).  Never changes a result."""
+    _check(LIB.ttemb_set_exact_grid(workgroups))
+
+
+def forward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Tensor, B: int, output: torch.Tensor,
+                  ws: Workspace) -> None:
+    """Bit-reproducible forward (``ttemb_forward_exact``): ``output`` [B, D] fully written."""
+    nnz = indices.numel()
+    dev = output.device
+    w = ws.get(exact_workspace_bytes(shape, nnz, B), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_forward_exact(ctypes.byref(shape), _ptr_array(cores), _ptr(indices), _ptr(offsets), nnz, B,
+                                       _ptr(output), _ptr(w), w.numel(), None, 0, _stream(output)))
+
+
+def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Tensor, B: int, d_output: torch.Tensor,
+                   ws: Workspace, d_cores=None, opt_state=None, lr: float = 0.0, eps: float = 0.0) -> None:
+    """Bit-reproducible backward: dense gradients into ``d_cores`` (every row written), else the fused step on the rows
+    the ids touch (Adagrad when ``opt_state`` is given)."""
+    nnz = indices.numel()
+    dev = d_output.device
+    w = ws.get(exact_workspace_bytes(shape, nnz, B), dev)
+    head = (ctypes.byref(shape), _ptr_array(cores))
+    ids = (_ptr(indices), _ptr(offsets), nnz, B, _ptr(d_output))
+    tail = (_ptr(w), w.numel(), None, 0, _stream(d_output))
+    with _on_device(dev):
+        if d_cores is not None:
+            _check(LIB.ttemb_backward_dense_exact(*head, *ids, _ptr_array(d_cores), *tail))
+        elif opt_state is None:
+            _check(LIB.ttemb_backward_sgd_exact(*head, *ids, lr, *tail))
+        else:
+            _check(LIB.ttemb_backward_adagrad_exact(*head, _ptr_array(opt_state), *ids, lr, eps, *tail))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

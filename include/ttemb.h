@@ -395,6 +395,53 @@ int ttemb_cache_backward_rowwise_adagrad(const int32_t* cache_loc, const int64_t
                                          float* cache_state_sum, float* cache_weight,
                                          void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Exact mode (OptimType.EXACT_SGD, FBTT/tt_embeddings_ops.py: "deterministic updates (via sorting + segment
+ * reduction)").  A kernel family of its own (ttemb_exact.hip): the outputs, gradients, updated cores and optimizer state
+ * are a function of (shape, cores, indices, offsets, B, d_output, lr, eps) only, bit for bit.  Nothing that sets a
+ * floating-point summation order depends on the grid size or the number of CUs, on workgroup scheduling or other work on
+ * the GPU, on the previous contents of the workspace, or on whether the call is eager or replayed from a captured graph:
+ *   - no float atomics; the only atomics are the integer digit counts of the sort, whose order sets nothing;
+ *   - no waits between workgroups (no look-back, no spin): nothing can expire, there is no poisoned plan to report;
+ *   - every loop over work items is grid-stride, and every chunk boundary comes from the sorted id list alone;
+ *   - no host synchronisation and no allocation (like every other lookup: an exact call can be captured).
+ * Forward: one wave per bag sums its ids' rows in position order and stores the bag row once (empty bags: zeros).
+ * Backward: the positions are sorted by i0, by i1 and by i2 (stable LSD radix sort: positions in order inside a row);
+ * each core row sums its ids' contributions in that order, in fixed chunks of the sorted list whose partials are added in
+ * chunk order.  Dense: every row of d_cores is written (untouched rows 0).  SGD / Adagrad: only the rows some id touches
+ * are updated; every other row and its optimizer state stay bitwise unchanged.
+ * Domain: 3-core views with q0, q2 <= 16, q0 q1 <= 64 and ranks <= 32 (any rank in that range, no padding).  A 2-core
+ * table runs with an identity middle core.  A 4-core table merges one adjacent pair into a virtual core (workspace; each
+ * element a sum in a fixed order), the pair chosen as the one whose view fits with the smallest virtual core, and its
+ * gradient is split back into the pair's gradients in a fixed order.  TTEMB_E_UNSUPPORTED with a message for everything
+ * else (ranks 64..256, larger q, a 4-core table none of whose pairs gives such a view) and for a call without `offsets`
+ * (int64[B+1], required; the ids are the concatenated bags).  A live LFU cache is the caller's to exclude: these calls
+ * never look at one.
+ * Workspace: ttemb_exact_workspace_bytes() serves the forward and every backward; only a 4-core table's forward uses it.
+ * `plan` / `plan_bytes` are reserved: ttemb_exact_plan_bytes() is 0 today and the calls ignore the two arguments (pass
+ * NULL, 0).  The backward sorts the ids itself and forms every product from the cores it is given; a later version may
+ * keep the sort and the group products there, sized by ttemb_exact_plan_bytes(), without changing these signatures.
+ * ------------------------------------------------------------------------------- */
+int64_t ttemb_exact_workspace_bytes(const ttemb_shape_t* shape, int64_t nnz, int64_t B);   /* forward and backward */
+int64_t ttemb_exact_plan_bytes(const ttemb_shape_t* shape, int64_t nnz);
+/* DIAGNOSTIC, process-wide: caps the grid of every exact kernel at `workgroups` (0 = the default).  Under the contract it
+ * never changes a result; tests use it to show that. */
+int ttemb_set_exact_grid(int32_t workgroups);
+int ttemb_forward_exact(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices,
+                        const int64_t* offsets, int64_t nnz, int64_t B, float* output,
+                        void* workspace, int64_t workspace_bytes, void* plan, int64_t plan_bytes, void* stream);
+int ttemb_backward_dense_exact(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices,
+                               const int64_t* offsets, int64_t nnz, int64_t B, const float* d_output,
+                               float* const* d_cores, void* workspace, int64_t workspace_bytes,
+                               const void* plan, int64_t plan_bytes, void* stream);
+int ttemb_backward_sgd_exact(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices,
+                             const int64_t* offsets, int64_t nnz, int64_t B, const float* d_output, float lr,
+                             void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream);
+int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state,
+                                 const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
+                                 const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes,
+                                 const void* plan, int64_t plan_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
