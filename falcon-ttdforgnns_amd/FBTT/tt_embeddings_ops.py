@@ -462,6 +462,60 @@ class _ExactLookup(torch.autograd.Function):
         return (None,) * n_fixed + tuple(full)
 
 
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """Contiguous float32 at a 16-byte address: what the bag kernels' float4 accesses need (a gradient can arrive as a view)."""
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.contiguous().float()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _WeightedBag(torch.autograd.Function):
+    """``mode="sum"`` with ``per_sample_weights``: ``out[b] = sum_{i in bag b} w[i] rows[i]`` over the looked-up rows of
+    bags of one (``ttemb_bag_reduce``).  The backward hands ``d_rows[i] = w[i] dOut[bag(i)]`` to the lookup's own backward
+    (fused step, dense gradients, bucket, exact -- whatever produced ``rows``) and, when ``w`` needs it,
+    ``w.grad[i] = <dOut[bag(i)], rows[i]>`` from the same pass.  ``rows`` is kept only for that weight gradient."""
+
+    @staticmethod
+    def forward(ctx, rows: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor,
+                module: "TableBatchedTTEmbeddingBag") -> torch.Tensor:
+        out = torch.empty((offsets.numel() - 1, rows.shape[1]), dtype=torch.float32, device=rows.device)
+        _nat.bag_reduce(rows, weights, offsets, out, module._ws)
+        ctx.module, ctx.offsets = module, offsets
+        ctx.save_for_backward(weights, rows if ctx.needs_input_grad[1] else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        weights, rows = ctx.saved_tensors
+        d_output = _aligned(d_output)
+        d_rows = torch.empty((weights.numel(), d_output.shape[-1]), dtype=torch.float32, device=d_output.device)
+        d_w = torch.empty_like(weights) if ctx.needs_input_grad[1] else None
+        _nat.bag_reduce_backward(d_output, weights, ctx.offsets, d_rows, ctx.module._ws, rows=rows, d_weights=d_w)
+        return d_rows, d_w, None, None
+
+
+class _BagMean(torch.autograd.Function):
+    """``mode="mean"``: the bag sums of the plain lookup divided by the bag lengths in place (``ttemb_bag_mean``); the
+    backward divides ``dOut`` the same way into scratch for the lookup's backward.  ``sums`` is [..., B', D] with
+    ``offsets`` of its B' bags."""
+
+    @staticmethod
+    def forward(ctx, sums: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        flat = sums.view(-1, sums.shape[-1])
+        _nat.bag_mean(flat, flat, offsets)
+        ctx.offsets = offsets
+        ctx.mark_dirty(sums)
+        return sums
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        d_output = _aligned(d_output)
+        d_sums = torch.empty_like(d_output)
+        D = d_output.shape[-1]
+        _nat.bag_mean(d_output.view(-1, D), d_sums.view(-1, D), ctx.offsets)
+        return d_sums, None
+
+
 class _ReplayLookup(torch.autograd.Function):
     """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each."""
 
@@ -485,11 +539,13 @@ class CapturedLookup:
     literal "batch 2048": ~25 us of kernels under ~75-115 us of eager host work).  Call it like the module:
     ``out = cap(indices[, offsets])``; ``out`` is a static buffer that the next call overwrites (as with
     ``torch.cuda.make_graphed_callables``).  The workspace and plan the graphs were captured with are owned by this object,
-    so other calls on the module cannot move them.  ``sparse=True`` modules with one table and no live cache."""
+    so other calls on the module cannot move them.  ``sparse=True`` modules with one table and no live cache.  A captured
+    lookup is the unweighted ``mode="sum"`` call: it takes no ``per_sample_weights``, and a ``mode="mean"`` module is refused."""
 
     def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, offsets: Optional[torch.Tensor] = None) -> None:
         assert module.sparse and module.num_tables == 1, "capture() covers the fused-optimiser mode of a single table"
         assert not (module.use_cache and not module.warmup), "capture() with a live row cache is not supported"
+        assert module.mode == "sum", "capture() covers mode='sum' (unweighted)"
         self.module, self.nnz, self.B = module, int(nnz), int(B)
         dev = module.tt_cores[0].device
         self.indices = torch.zeros(self.nnz, dtype=torch.int64, device=dev)
@@ -569,6 +625,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     Constructor / attribute contract: reference tt_embeddings_ops.py:446-615.
     ``forward(indices, offsets)`` returns ``[num_tables, B, D]`` sum-pooled bags with
     ``include_last_offset`` semantics (``offsets`` has ``num_tables*B + 1`` entries).
+
+    ``mode`` (keyword-only) and ``forward(..., per_sample_weights=w)`` follow ``torch.nn.functional.embedding_bag``:
+    ``mode="sum"`` with ``w`` (float32 ``[nnz]``) pools ``w[i] * row(indices[i])``, ``mode="mean"`` divides each bag sum by
+    the bag's length (an empty bag gives zeros).  Weights with ``mode="mean"`` raise ``ValueError``.  Gradients reach the
+    cores through every optimiser mode, and ``w.grad`` when ``w`` requires it.
     """
 
     __constants__ = ["num_tables", "num_embeddings", "embedding_dim", "tt_shape", "tt_rank"]
@@ -578,8 +639,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000, *, deterministic: Optional[bool] = None) -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum") -> None:
         super().__init__()
+        if mode not in ("sum", "mean"):
+            raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
+        self.mode = mode
         # exact mode (``_ExactLookup``): True / False, or None = on for OptimType.EXACT_SGD and whenever
         # torch.are_deterministic_algorithms_enabled() at call time
         self.deterministic = deterministic
@@ -795,8 +859,62 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         return TTLookupFunction.apply(self, table, B, part, rowidx, offsets, nnz_tt, loc, self.cache_weight,
                                       *self.tt_cores)
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True) -> torch.Tensor:
+    def _bags_of_one(self, nnz: int, dev: torch.device) -> torch.Tensor:
+        """offsets 0, 1, ..., nnz (module scratch, grown when a call is longer; not part of the state dict)."""
+        a = getattr(self, "_arange", None)
+        if a is None or a.device != dev or a.numel() < nnz + 1:
+            a = self._arange = torch.arange(nnz + 1, dtype=torch.int64, device=dev)
+        return a[: nnz + 1]
+
+    def _weighted_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, weights: torch.Tensor,
+                            exact: bool) -> torch.Tensor:
+        """One row per id (the lookup of nnz bags of one, through whichever autograd bridge serves the call), then the
+        weighted bag sums of ``_WeightedBag``."""
+        nnz = indices.numel()
+        rows = self._lookup_one_table(table, nnz, indices, self._bags_of_one(nnz, indices.device), exact)
+        return _WeightedBag.apply(rows, weights, offsets, self)
+
+    def _pooled(self, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
+                tables_dim: bool) -> torch.Tensor:
+        """``forward`` with ``per_sample_weights`` or in ``mode="mean"``; ``tables_dim``: return [num_tables, B, D]."""
+        if not indices.is_cuda:
+            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
+        if weights is not None:
+            if self.mode != "sum":
+                raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
+                                 "(as in torch.nn.functional.embedding_bag)")
+            _nat._check_weights(weights, indices.numel(), indices)   # before anything is launched
+            weights = weights.contiguous()
+        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
+        assert (offsets.numel() - 1) % self.num_tables == 0
+        T, B = self.num_tables, (offsets.numel() - 1) // self.num_tables
+        if not self._fused_probe():
+            self.update_cache(indices)
+        exact = self._exact_active()
+        if weights is None:   # mean: today's bag sums (no host synchronisation wherever the lookup has none), then / len
+            sums = (self._lookup_one_table(0, B, indices, offsets, exact) if T == 1
+                    else self._lookup_tables(indices, offsets, B, exact))
+            out = _BagMean.apply(sums, offsets)
+        elif T == 1:
+            out = self._weighted_one_table(0, indices, offsets, weights, exact)
+        elif B == 0:
+            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=indices.device)
+        else:
+            # several tables with weights: the id list is split on the host (one synchronisation), one call per table
+            bounds = offsets[:: B].tolist()
+            outs = []
+            for k in range(T):
+                lo, hi = int(bounds[k]), int(bounds[k + 1])
+                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
+                outs.append(self._weighted_one_table(k, indices[lo:hi].contiguous(), offs_k, weights[lo:hi], exact))
+            out = torch.stack(outs, 0)
+        return out.unsqueeze(0) if tables_dim and T == 1 else out
+
+    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True, *,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # `warmup` is accepted and ignored, like the reference (it reads self.warmup, :862)
+        if per_sample_weights is not None or self.mode != "sum":
+            return self._pooled(indices, offsets, per_sample_weights, True)
         if not indices.is_cuda:
             raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
         indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
@@ -807,6 +925,10 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         exact = self._exact_active()
         if self.num_tables == 1:
             return self._lookup_one_table(0, B, indices, offsets, exact).unsqueeze(0)
+        return self._lookup_tables(indices, offsets, B, exact)
+
+    def _lookup_tables(self, indices: torch.Tensor, offsets: torch.Tensor, B: int, exact: bool) -> torch.Tensor:
+        """[num_tables, B, D] bag sums of a module with several tables."""
         # every table is a window of the id list, its bounds read from `offsets` on the device (no host synchronisation) -- when the
         # grouped kernels serve the shape; else the id list is split on the host, one plain lookup per table
         nnz = indices.numel()
@@ -831,14 +953,17 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = True, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000, *, deterministic: Optional[bool] = None) -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum") -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
-                         enforce_embedding_dim, batch_count, deterministic=deterministic)
+                         enforce_embedding_dim, batch_count, deterministic=deterministic, mode=mode)
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True) -> torch.Tensor:
+    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True, *,
+                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # same result as the reference's ``super().forward(...)[0]`` (:960-965) without the
         # [1, B, D] view: selecting table 0 would cost a zero-fill + copy of B*D floats in backward
+        if per_sample_weights is not None or self.mode != "sum":
+            return self._pooled(indices, offsets, per_sample_weights, False)
         if not indices.is_cuda:
             raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
         if indices.dtype != torch.int64 or not indices.is_contiguous():

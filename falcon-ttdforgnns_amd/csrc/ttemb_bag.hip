@@ -1,0 +1,263 @@
+// Bag pooling around the lookups: per-sample weights (mode "sum") and mean pooling (include/ttemb.h, "Weighted and mean
+// bags").  The TT kernels are not touched: a weighted call looks up one row per id (bags of one) and reduces those rows
+// here; a mean call divides the bag sums of the plain lookup by the bag lengths.
+//
+//   reduce     out[b] = sum_{i in bag b} w[i] rows[i], ids in position order.  A bag of at most kBagChunk ids is summed
+//              by one lane group; a longer bag is cut into the fixed chunks [k C, (k+1) C) of the position list
+//              (bag_partial_kernel writes one partial per chunk it reaches) and its partials are added in chunk order.
+//   backward   d_rows[i] = w[i] dOut[bag(i)] and d_w[i] = <dOut[bag(i)], rows[i]> in one pass, one lane group per id.
+//   mean       dst[b] = src[b] / len(b), zeros for an empty bag.
+//
+// Every kernel is deterministic by construction, in the sense of the exact-mode contract: no float atomics, no waits
+// between workgroups, grid-stride loops over work items (the grid decides who computes a value, never how), summation
+// orders set by `offsets` (and D) alone, and every workspace word that is read was written earlier in the same call.
+// Their grids honour ttemb_set_exact_grid.
+//
+// Lane groups: a group of W lanes (W = the power of two >= D / 4, at most 64) owns one bag / chunk / id and walks its
+// row in float4 columns, W at a time; a workgroup holds kBagNT / W groups.
+#include "ttemb_common.h"
+
+namespace ttemb {
+namespace bag {
+
+constexpr int kBagNT = 256;               // threads per workgroup
+constexpr int64_t kBagChunk = 512;        // ids per chunk of a long bag
+constexpr int64_t kBagHeader = kFast3HeaderBytes;   // the workspace header of the grouped lookups: never written here
+
+struct Groups {
+  int shift;   // log2(W)
+  int per_block;
+};
+
+Groups groups_of(int64_t D4) {
+  int shift = 0;
+  while ((int64_t(1) << shift) < D4 && shift < 6) ++shift;
+  return Groups{shift, kBagNT >> shift};
+}
+
+__device__ __forceinline__ float4 f4_scale(float w, float4 r) { return make_float4(w * r.x, w * r.y, w * r.z, w * r.w); }
+
+__device__ __forceinline__ float4 f4_fma(float w, float4 r, float4 a) {
+  return make_float4(fmaf(w, r.x, a.x), fmaf(w, r.y, a.y), fmaf(w, r.z, a.z), fmaf(w, r.w, a.w));
+}
+
+__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// [n0, n1) of bag b, clamped to the id list (a bag past the list is empty)
+__device__ __forceinline__ void bag_range(const int64_t* __restrict__ offsets, int64_t nnz, int64_t b, int64_t& n0, int64_t& n1) {
+  n0 = offsets[b];
+  n1 = offsets[b + 1];
+  n0 = n0 < 0 ? 0 : (n0 > nnz ? nnz : n0);
+  n1 = n1 < n0 ? n0 : (n1 > nnz ? nnz : n1);
+}
+
+// sum_{i in [a, e)} w[i] rows[i][c], i in order (a < e): the first term a product, then one fma per id
+__device__ __forceinline__ float4 weighted_sum(const float4* __restrict__ rows, const float* __restrict__ w, int64_t D4,
+                                               int64_t c, int64_t a, int64_t e) {
+  float4 acc = f4_scale(w[a], rows[a * D4 + c]);
+#pragma unroll 8
+  for (int64_t i = a + 1; i < e; ++i) acc = f4_fma(w[i], rows[i * D4 + c], acc);
+  return acc;
+}
+
+// Chunk k = positions [k C, (k+1) C): the part of every LONG bag (more than C ids) that lies in it goes to one of the
+// chunk's two slots -- slot 0 for the bag that began before the chunk, slot 1 for the bag that begins inside it (a long bag
+// cannot lie wholly inside a chunk, so there are at most these two).  Short bags are summed by bag_reduce_kernel.
+__global__ __launch_bounds__(kBagNT) void bag_partial_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
+                                                             const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                             int64_t D4, int shift, int64_t nchunks,
+                                                             float4* __restrict__ partial) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
+    const int64_t s = k * kBagChunk, e = s + kBagChunk < nnz ? s + kBagChunk : nnz;
+    const int64_t bs = bag_of_position(offsets, B, s), be = bag_of_position(offsets, B, e - 1);
+    for (int which = 0; which < 2; ++which) {
+      const int64_t b = which == 0 ? bs : be;
+      if (which == 1 && be == bs) break;
+      int64_t n0, n1;
+      bag_range(offsets, nnz, b, n0, n1);
+      const int64_t a = n0 > s ? n0 : s, z = n1 < e ? n1 : e;
+      if (n1 - n0 <= kBagChunk || a >= z) continue;
+      float4* dst = partial + (2 * k + (n0 < s ? 0 : 1)) * D4;
+      for (int64_t c = lane; c < D4; c += W) dst[c] = weighted_sum(rows, w, D4, c, a, z);
+    }
+  }
+}
+
+// out[b]: a bag of one id is a scale and a store; a short bag one sum in position order; a long bag the sum of its chunk
+// partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); an empty bag zeros.
+__global__ __launch_bounds__(kBagNT) void bag_reduce_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
+                                                            const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                            int64_t D4, int shift, const float4* __restrict__ partial,
+                                                            float4* __restrict__ out) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
+    int64_t n0, n1;
+    bag_range(offsets, nnz, b, n0, n1);
+    float4* dst = out + b * D4;
+    if (n1 - n0 > kBagChunk) {
+      const int64_t k0 = n0 / kBagChunk, k1 = (n1 - 1) / kBagChunk;
+      for (int64_t c = lane; c < D4; c += W) {
+        float4 acc = partial[(2 * k0 + 1) * D4 + c];
+#pragma unroll 8
+        for (int64_t k = k0 + 1; k <= k1; ++k) acc = f4_add(acc, partial[2 * k * D4 + c]);
+        dst[c] = acc;
+      }
+    } else if (n1 > n0) {
+      for (int64_t c = lane; c < D4; c += W) dst[c] = weighted_sum(rows, w, D4, c, n0, n1);
+    } else {
+      for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+  }
+}
+
+// d_rows[i] = w[i] dOut[bag(i)]; d_w[i] = <dOut[bag(i)], rows[i]> (each lane sums its columns in order, then a butterfly
+// over the group's W lanes: a fixed tree for a given D).  An id outside every bag gets zeros.
+__global__ __launch_bounds__(kBagNT) void bag_reduce_backward_kernel(const float4* __restrict__ d_out,
+                                                                     const float* __restrict__ w,
+                                                                     const float4* __restrict__ rows,
+                                                                     const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                     int64_t B, int64_t D4, int shift,
+                                                                     float4* __restrict__ d_rows, float* __restrict__ d_w) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  const int64_t first = offsets[0], last = offsets[B];
+  const int64_t passes = (D4 + W - 1) >> shift;
+  for (int64_t i = (int64_t)blockIdx.x * per_block + g; i < nnz; i += (int64_t)gridDim.x * per_block) {
+    const bool in_bag = i >= first && i < last;
+    const int64_t b = in_bag ? bag_of_position(offsets, B, i) : 0;
+    const float wi = w[i];
+    float dot = 0.0f;
+    for (int64_t k = 0; k < passes; ++k) {   // the same trip count on every lane of the group (the butterfly needs them all)
+      const int64_t c = lane + (k << shift);
+      if (c < D4) {
+        const float4 gv = in_bag ? d_out[b * D4 + c] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        d_rows[i * D4 + c] = f4_scale(wi, gv);
+        if (d_w != nullptr) {
+          const float4 r = rows[i * D4 + c];
+          dot = fmaf(gv.x, r.x, dot);
+          dot = fmaf(gv.y, r.y, dot);
+          dot = fmaf(gv.z, r.z, dot);
+          dot = fmaf(gv.w, r.w, dot);
+        }
+      }
+    }
+    if (d_w != nullptr) {
+      for (int m = W >> 1; m > 0; m >>= 1) dot += __shfl_xor(dot, m, W);
+      if (lane == 0) d_w[i] = dot;
+    }
+  }
+}
+
+// dst[b] = src[b] / len(b) (a division, as torch's mean bags); an empty bag gives zeros whatever src holds
+__global__ __launch_bounds__(kBagNT) void bag_mean_kernel(const float4* src, float4* dst, const int64_t* __restrict__ offsets,
+                                                          int64_t B, int64_t D4, int shift) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
+    const int64_t len = offsets[b + 1] - offsets[b];
+    const float n = (float)len;
+    for (int64_t c = lane; c < D4; c += W) {
+      const float4 v = src[b * D4 + c];
+      dst[b * D4 + c] = len > 0 ? make_float4(v.x / n, v.y / n, v.z / n, v.w / n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+  }
+}
+
+int64_t chunks_of(int64_t nnz) { return (nnz + kBagChunk - 1) / kBagChunk; }
+
+unsigned grid_of(int64_t items, const Groups& gr) { return exact::ex_grid((items + gr.per_block - 1) / gr.per_block); }
+
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+int check_sizes(const char* what, int64_t nnz, int64_t B, int64_t D) {
+  if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "%s: negative nnz / B", what);
+  if (D <= 0 || D % 4 != 0) return fail(TTEMB_E_BADARG, "%s: D = %lld is not a positive multiple of 4", what, (long long)D);
+  return TTEMB_OK;
+}
+
+}  // namespace bag
+}  // namespace ttemb
+
+using namespace ttemb;
+using namespace ttemb::bag;
+
+extern "C" {
+
+int64_t ttemb_bag_workspace_bytes(int64_t nnz, int64_t B, int64_t D) {
+  int rc = check_sizes("ttemb_bag_workspace_bytes", nnz, B, D);
+  if (rc) return rc;
+  return kBagHeader + 2 * chunks_of(nnz) * D * (int64_t)sizeof(float);
+}
+
+int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, int64_t B, int64_t D,
+                     float* output, void* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes("ttemb_bag_reduce", nnz, B, D);
+  if (rc) return rc;
+  if (B == 0) return TTEMB_OK;
+  if (offsets == nullptr || output == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: offsets / output is null");
+  if (nnz > 0 && (rows == nullptr || weights == nullptr))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: rows / weights is null");
+  if (misaligned(rows) || misaligned(output)) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: rows / output not 16-byte aligned");
+  const int64_t need = ttemb_bag_workspace_bytes(nnz, B, D);
+  if (workspace_bytes < need || workspace == nullptr)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_reduce: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+                (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4, nch = chunks_of(nnz);
+  const Groups gr = groups_of(D4);
+  float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
+  const float4* r4 = reinterpret_cast<const float4*>(rows);
+  if (nch > 0) {
+    hipLaunchKernelGGL(bag_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, B, D4,
+                       gr.shift, nch, partial);
+    if ((rc = check_hip(hipGetLastError(), "bag_partial_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(bag_reduce_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, B, D4, gr.shift,
+                     partial, reinterpret_cast<float4*>(output));
+  return check_hip(hipGetLastError(), "bag_reduce_kernel");
+}
+
+int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const float* rows, const int64_t* offsets,
+                              int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  int rc = check_sizes("ttemb_bag_reduce_backward", nnz, B, D);
+  if (rc) return rc;
+  if (nnz == 0) return TTEMB_OK;
+  if (offsets == nullptr || weights == nullptr || d_rows == nullptr || (B > 0 && d_output == nullptr))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_backward: offsets / weights / d_rows / d_output is null");
+  if (d_weights != nullptr && rows == nullptr)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_backward: the weight gradient needs the rows");
+  if (misaligned(d_output) || misaligned(rows) || misaligned(d_rows))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_backward: d_output / rows / d_rows not 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4;
+  const Groups gr = groups_of(D4);
+  hipLaunchKernelGGL(bag_reduce_backward_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st,
+                     reinterpret_cast<const float4*>(d_output), weights, reinterpret_cast<const float4*>(rows), offsets, nnz,
+                     B, D4, gr.shift, reinterpret_cast<float4*>(d_rows), d_weights);
+  return check_hip(hipGetLastError(), "bag_reduce_backward_kernel");
+}
+
+int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t B, int64_t D, void* stream) {
+  int rc = check_sizes("ttemb_bag_mean", 0, B, D);
+  if (rc) return rc;
+  if (B == 0) return TTEMB_OK;
+  if (src == nullptr || dst == nullptr || offsets == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_mean: null pointer");
+  if (misaligned(src) || misaligned(dst)) return fail(TTEMB_E_BADARG, "ttemb_bag_mean: src / dst not 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const Groups gr = groups_of(D / 4);
+  hipLaunchKernelGGL(bag_mean_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, reinterpret_cast<const float4*>(src),
+                     reinterpret_cast<float4*>(dst), offsets, B, D / 4, gr.shift);
+  return check_hip(hipGetLastError(), "bag_mean_kernel");
+}
+
+}  // extern "C"

@@ -138,6 +138,12 @@ int launch_forward_small3(const DevShape& s, const CorePtrs& cores, const int64_
 int launch_backward_small3(const DevShape& s, const CorePtrs& cores, const int64_t* indices, const int64_t* offsets, int64_t nnz,
                            const int32_t* nnz_dev, int64_t B, const float* d_output, const CorePtrsMut& d_cores, hipStream_t st);
 
+// grid of a deterministic kernel over `items` workgroups' worth of work, capped by ttemb_set_exact_grid (ttemb_exact.hip;
+// the bag kernels of ttemb_bag.hip use it too)
+namespace exact {
+unsigned ex_grid(int64_t items);
+}
+
 // zero `bytes` (a multiple of 4) at `p` with a kernel on `st`.  Used instead of hipMemsetAsync everywhere: inside a
 // captured HIP graph (ROCm 7.2) a memset node was seen to race the kernel node that follows it.
 int launch_zero(void* p, size_t bytes, hipStream_t st, const char* what);

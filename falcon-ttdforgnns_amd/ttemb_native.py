@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_cache_backward_dense", "ttemb_cache_backward_rowwise_adagrad",
     "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_set_exact_grid", "ttemb_forward_exact",
     "ttemb_backward_dense_exact", "ttemb_backward_sgd_exact", "ttemb_backward_adagrad_exact",
+    "ttemb_bag_workspace_bytes", "ttemb_bag_reduce", "ttemb_bag_reduce_backward", "ttemb_bag_mean",
 )
 
 
@@ -121,10 +122,15 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_backward_dense_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_sgd_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, f32, vp, i64, vp, i64, vp]
     lib.ttemb_backward_adagrad_exact.argtypes = [shp, vp, vp, vp, vp, i64, i64, vp, f32, f32, vp, i64, vp, i64, vp]
+    lib.ttemb_bag_workspace_bytes.restype = i64
+    lib.ttemb_bag_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.ttemb_bag_reduce.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_backward.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_mean.argtypes = [vp, vp, vp, i64, i64, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
-                        "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes"):
+                        "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -510,6 +516,69 @@ def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Te
             _check(LIB.ttemb_backward_sgd_exact(*head, *ids, lr, *tail))
         else:
             _check(LIB.ttemb_backward_adagrad_exact(*head, _ptr_array(opt_state), *ids, lr, eps, *tail))
+
+
+def bag_workspace_bytes(nnz: int, B: int, D: int) -> int:
+    """Bytes ``bag_reduce`` needs (behind the lookups' 40 KB header: the lookups' workspace serves it too)."""
+    key = ("bag", nnz, B, D)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_bag_workspace_bytes(nnz, B, D))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def _check_weights(weights: torch.Tensor, nnz: int, ref: torch.Tensor) -> None:
+    if weights.dtype != torch.float32 or weights.dim() != 1 or weights.numel() != nnz or weights.device != ref.device:
+        raise ValueError(f"per_sample_weights must be float32 of shape [{nnz}] on {ref.device}, got "
+                         f"{weights.dtype} {list(weights.shape)} on {weights.device}")
+
+
+def _check_sizes(tensors, n: int) -> None:
+    for t in tensors:
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n):
+            raise ValueError(f"bag pooling: expected float32 with {n} elements, got {t.dtype} {list(t.shape)}")
+
+
+def bag_reduce(rows: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, ws: Workspace) -> None:
+    """``output[b] = sum_{i in bag b} weights[i] rows[i]`` (``ttemb_bag_reduce``): rows [nnz, D], output [B, D] fully written."""
+    nnz, D = rows.shape
+    B = offsets.numel() - 1
+    _check_weights(weights, nnz, rows)
+    _check_sizes((output,), B * D)
+    dev = output.device
+    w = ws.get(bag_workspace_bytes(nnz, B, D), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_bag_reduce(_ptr(rows), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(w), w.numel(),
+                                    _stream(output)))
+
+
+def bag_reduce_backward(d_output: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor,
+                        ws: Workspace, rows: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None) -> None:
+    """``d_rows[i] = weights[i] d_output[bag(i)]``, and ``d_weights[i] = <d_output[bag(i)], rows[i]>`` when ``d_weights``
+    is given (then ``rows`` is needed); one pass (``ttemb_bag_reduce_backward``)."""
+    nnz, D = d_rows.shape
+    B = offsets.numel() - 1
+    _check_weights(weights, nnz, d_rows)
+    _check_sizes((d_output,), B * D)
+    _check_sizes((rows,), nnz * D)
+    if d_weights is not None:
+        _check_sizes((d_weights,), nnz)
+    dev = d_rows.device
+    w = ws.get(0, dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_bag_reduce_backward(_ptr(d_output), _ptr(weights), _ptr(rows), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                             _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
+
+
+def bag_mean(src: torch.Tensor, dst: torch.Tensor, offsets: torch.Tensor) -> None:
+    """``dst[b] = src[b] / len(b)``, zeros for an empty bag (``ttemb_bag_mean``); ``dst`` may be ``src``."""
+    D, B = src.shape[-1], offsets.numel() - 1
+    _check_sizes((src, dst), B * D)
+    with _on_device(dst.device):
+        _check(LIB.ttemb_bag_mean(_ptr(src), _ptr(dst), _ptr(offsets), B, D, _stream(dst)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

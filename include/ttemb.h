@@ -442,6 +442,34 @@ int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores
                                  const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes,
                                  const void* plan, int64_t plan_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Weighted and mean bags (torch.nn.functional.embedding_bag with include_last_offset=True: mode "sum" with
+ * per_sample_weights, and mode "mean").  These calls pool rows the lookups produced; they never read a core (ttemb_bag.hip).
+ *   - weighted sum: look the ids up as nnz bags of one (offsets = 0, 1, ..., nnz), then
+ *     ttemb_bag_reduce: output[b] = sum_{i in bag b} weights[i] rows[i], ids in position order; the backward
+ *     ttemb_bag_reduce_backward writes d_rows[i] = weights[i] d_output[bag(i)] (which any lookup backward then takes with
+ *     the same bags of one) and, when d_weights is not NULL, d_weights[i] = <d_output[bag(i)], rows[i]>;
+ *   - mean: the plain lookup with the real offsets, then ttemb_bag_mean: dst[b] = src[b] / len(b) (a division; dst may
+ *     alias src); the backward is ttemb_bag_mean on d_output into scratch, then the plain lookup backward.
+ * rows / d_rows are float32 [nnz][D], output / d_output / src / dst [B][D], weights / d_weights float32 [nnz], offsets
+ * int64 [B + 1] over the concatenated bags.  D is a positive multiple of 4 and the [.][D] buffers are 16-byte aligned.
+ * An empty bag gives zeros; an id outside every bag gets zero d_rows / d_weights.
+ * Deterministic by construction, as exact mode: no float atomics, no waits between workgroups, grid-stride loops whose
+ * grid is capped by ttemb_set_exact_grid, summation orders set by `offsets` and D alone.  A bag of more than 512 ids is
+ * summed in the fixed chunks [512 k, 512 (k + 1)) of the position list, whose partials (workspace) are added in chunk order.
+ * ttemb_bag_workspace_bytes sizes the workspace of ttemb_bag_reduce; it lies behind the 40 KB header, so the workspace of
+ * the lookups serves these calls too.  ttemb_bag_reduce_backward does not use its workspace today (pass the same one).
+ * No host synchronisation and no allocation.
+ * ------------------------------------------------------------------------------- */
+int64_t ttemb_bag_workspace_bytes(int64_t nnz, int64_t B, int64_t D);
+int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, int64_t B, int64_t D,
+                     float* output, void* workspace, int64_t workspace_bytes, void* stream);
+int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const float* rows /* NULL: no d_weights */,
+                              const int64_t* offsets, int64_t nnz, int64_t B, int64_t D, float* d_rows,
+                              float* d_weights /* NULL: no weight gradient */, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t B, int64_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
