@@ -143,28 +143,31 @@ __device__ __forceinline__ uint4 load_desc(desc_ptr tab, uint32_t c, uint32_t nc
 // ---------------------------------------------------------------------------------
 // Grouping pass: a two-digit counting sort of the live ids by group' = i1 * p0 + i0, cut into chunks.
 //   value = output row | kMultiBit when the bag holds several ids.
-// ids of one (i0, i1) group end up adjacent, consecutive groups share i1.  THREE launches, no device-wide scan, no global
+// ids of one (i0, i1) group end up adjacent, consecutive groups share i1.  TWO launches, no device-wide scan, no global
 // atomic per id (one returning atomic per id capped the first version at ~16 G ids/s = 25 us; fire-and-forget ones run at
 // the same ~16 G/s), and nothing that has to be cleared before the call (round 2: five launches, one of them a 4.5 us
 // zero-fill of a few KB): every counter and flag the launches share is TAGGED with the call's epoch, a number kept on the
 // device (so that a replayed HIP graph counts on) -- a word with another tag reads as "not written yet".
-// The group space is cut into ranges of 2^shift groups (first digit), the id list into slices:
-//   decode   every id -> (group, i2, row | multi); LDS histogram of the slice over the ranges; the slice's place inside
-//            every range from one returning atomic per (slice, range) on the epoch-tagged range counters; the group is
-//            stamped with the epoch ("holds an id")                                                  [one workgroup per slice]
-//   spread   every id moves to its range (ranges in order, slices in arrival order inside a range): cursor[range] from a
-//            scan of the range counters + the slice's place, one returning LDS atomic per id.  The prefix products of the
-//            stamped groups ride in this launch (they depend on nothing the grouping computes)       [one workgroup per slice]
-//   place    LDS histogram of a range's ids over its groups + scan (ids per group, starts inside the range), every id to its
-//            final position with one returning LDS atomic, THEN a look back at the chunk totals the ranges before this one
-//            published (epoch-tagged), then the chunk descriptors                                    [one workgroup per range]
+// The group space is cut into ranges of 2^shift groups (first digit), the id list into slices; every (range, bank) owns a
+// BUCKET of fixed capacity at a place known before any id is counted (round 6: a third launch, `spread`, scanned the range
+// totals to find each range's base, and that scan was the launch boundary):
+//   decode   every id -> (group, i2, row | multi); LDS histogram of a round of the slice over the ranges; the round's place
+//            inside every (range, bank) from one returning atomic on the epoch-tagged range counters; every id straight
+//            from registers to bucket[range][bank][place + rank] -- or, past the bucket's capacity, to an OVERFLOW block
+//            reserved with one atomic per (round, range) and linked into the range's list by an atomic exchange; the group
+//            is stamped with the epoch ("holds an id")                                               [one workgroup per slice]
+//   place    the range's bucket entries and overflow blocks: LDS histogram over its groups + scan (ids per group, starts
+//            inside the range; the range's first position is a sum of the range counters), every id to its final position
+//            with one returning LDS atomic, THEN a look back at the chunk totals the ranges before this one published
+//            (epoch-tagged), then the chunk descriptors.  The prefix products of the stamped groups ride in this launch
+//                                                                                                    [one workgroup per range]
 // A chunk is <= 16 consecutive ids of one group; its 16-byte descriptor {position, group, length | flags, first
 // chunk of the next group} is all the chain kernels need to walk the grouped ids -- they read descriptors with
 // scalar loads and never decode a key, compare neighbours or shuffle.  The order of ids inside a group is slice
-// arrival order, then arrival order inside a slice: every consumer is insensitive to it except for fp32 summation order in
-// the backward.
+// arrival order per bank, banks in order, then arrival order inside a slice; ids that went to overflow blocks come after
+// the bucket's: every consumer is insensitive to it except for fp32 summation order in the backward.
 // ---------------------------------------------------------------------------------
-constexpr int kSortThreads = 1024;       // decode / spread: one workgroup per slice of the id list
+constexpr int kSortThreads = 1024;       // decode: one workgroup per slice of the id list
 #ifndef TTEMB_RANGE_THREADS
 #define TTEMB_RANGE_THREADS 512
 #endif
@@ -181,7 +184,13 @@ constexpr int kCountBanks = 8;                               // banks of range c
 // Epoch tag of a range counter: 38 bits above a 26-bit id count, the top bit always SET -- whatever a word held before
 // (zeros, all-ones cache locations, floats), adding a count to it cannot produce a valid tag by carry.
 __host__ __device__ __forceinline__ uint64_t counter_tag(uint64_t epoch) { return ((epoch & ((1ull << 37) - 1ull)) | (1ull << 37)) << 26; }
+// The overflow counter and the list heads: the same tag above a 28-bit slot number (an overflow area holds < 2^27 slots)
+constexpr int kOvfBits = 28;
+constexpr uint64_t kOvfMask = (1ull << kOvfBits) - 1ull;
+__host__ __device__ __forceinline__ uint64_t ovf_tag(uint64_t epoch) { return ((epoch & ((1ull << 35) - 1ull)) | (1ull << 35)) << kOvfBits; }
 constexpr uint32_t kNoGroup = 0xffffffffu;
+constexpr uint32_t kNoBlock = 0xffffffffu;   // end of an overflow list
+constexpr int kRoundIds = kSortThreads * 4;  // ids a decode workgroup holds in registers at once: one round of its slice
 
 // A call whose output (or d_output) tensor does not fit one 32-bit window of byte offsets -- 2^24 rows or 2 GiB, what the
 // chain kernels address through buffer descriptors -- or whose ids exceed what one grouping pass takes, runs as a sequence
@@ -200,24 +209,27 @@ struct Piece {
 
 struct GroupPlan {           // device pointers into the caller's plan buffer / workspace
   const Piece* piece;        // null: the call is one piece (positions from 0, rows from 0)
-  uint32_t* grp_in;          // [nnz] ungrouped: group of the id (kNoGroup past the live count)
-  uint32_t* i2_in;           // [nnz] ungrouped: last index digit
-  uint32_t* vals_in;         // [nnz] ungrouped: output row | kMultiBit
-  uint32_t* grp_mid;         // [nnz] the same three, ordered by range
-  uint32_t* i2_mid;
-  uint32_t* vals_mid;
-  uint32_t* shist;           // [slices][ranges] place of slice s inside range r (arrival order of the slices)
+  uint2* bucket;             // [ranges][banks][cap] {output row | kMultiBit, group - first group of the range | i2 << 16}: the
+                             //     fixed-capacity bucket of every (range, bank), filled in place order by the decode step.  Read as
+                             //     one 64-bit word an entry has bit 63 CLEAR (bit 31 of the key: key < 2^28), every tag of the pass
+                             //     has it set -- no entry a call leaves behind can read as a tagged word of a later call
+  uint2* ovf;                // [ovf_slots] overflow blocks: a header {len, next block} then len entries like the bucket's
+  uint64_t* ovf_count;       // header word: (overflow tag | slots reserved so far) -- one returning atomic per block
+  uint64_t* ovf_head;        // header words [kMaxRanges]: (overflow tag | first block of the range's list); another tag reads as
+                             //     "no block".  At a fixed place, written by nothing but the decode step
+  uint32_t cap;              // entries per (range, bank) bucket
+  uint32_t banks;            // banks in use: min(slices, kCountBanks)
+  uint32_t ovf_slots;
   uint64_t* rcount;          // [kCountBanks][kMaxRanges] (epoch tag | ids of the range so far, from the slices of the bank): the tag
                              //     makes a counter of an earlier call -- or whatever the memory held -- read as zero, so nothing
                              //     has to be cleared between calls.  Slices are dealt to the banks round-robin: the atomics of
                              //     200 slices on ONE counter per range were a serial chain of 200 memory-side operations
-                             //     (decode 19-23 us); eight banks make it 25 (and the spread step adds eight words per range)
-  uint32_t* rstart;          // [ranges + 1] first position of every range in the range-ordered arrays
+                             //     (decode 19-23 us); eight banks make it 25
   uint32_t* gstamp;          // [G] epoch (low word) of the last call that saw an id of the group (a stale or foreign word only
                              //     ever adds a prefix product nobody reads: it needs no clearing and no initial state)
   uint64_t* epochs;          // [2] the grouping pass's call counter, kept ON THE DEVICE so that a replayed HIP graph counts on:
-                             //     [0] the last finished call (read by decode / spread, written by place),
-                             //     [1] the running call (written by spread, read by place).  Any start value will do.
+                             //     [0] the last finished call (read by decode, written by place),
+                             //     [1] the running call (written by decode, read by place).  Any start value will do.
   uint64_t* rpub;            // [2 * ranges] (epoch << 24 | chunks of the range), then (epoch << 24 | its non-empty groups):
                              //     what a place workgroup publishes for the ranges after it
   uint32_t* i2s;             // [nnz] grouped: last index digit of the id
@@ -236,7 +248,7 @@ struct GroupPlan {           // device pointers into the caller's plan buffer / 
   uint32_t* epi_live;        // [slices][p1] sparse form only: 1 when the slice of that i1 holds an id (its slab exists)
   uint32_t* wrows;           // wide-rank chain: [p1][stride] the rows (i0, a) of every i1 whose group holds an id (wide3_rows_kernel)
   uint32_t* wnrows;          // [p1] their number
-  uint32_t* ticket;          // header word: the place step's range tickets (zeroed by the spread step of the same call)
+  uint32_t* ticket;          // header word: the place step's range tickets (zeroed by the decode step of the same call)
   uint32_t use_ticket;       // the place step draws its ranges from the ticket (the id-only half of a two-phase forward: the launch
                              //     that runs beside the data-parallel step's all-reduce) instead of taking its workgroup indices
   uint32_t* fault_host;      // pinned host word (device address) a bounded wait that ran out reports to, or null
@@ -259,7 +271,7 @@ struct GroupPlan {           // device pointers into the caller's plan buffer / 
 // from whatever their memory held: zeros, often), and a fault word a faulted call left in the buffer must not meet a later
 // call of ANOTHER workspace that happens to carry the same number.
 // ---------------------------------------------------------------------------------
-constexpr uint32_t kFaultTakeOver = 1u, kFaultLookBack = 2u;
+constexpr uint32_t kFaultTakeOver = 1u, kFaultLookBack = 2u, kFaultOverflow = 3u;
 __device__ __forceinline__ uint64_t plan_tag(const GroupPlan& plan, uint64_t call) {
   const uint64_t salt = (reinterpret_cast<uint64_t>(plan.epochs) >> 8) * 0x9e3779b97f4a7c15ull;
   return (((call + salt) & ((1ull << 39) - 1ull)) | (1ull << 39)) << 24;
@@ -324,15 +336,41 @@ __device__ __forceinline__ T block_exclusive(T v, T* wave_sums, T& total) {
   return before + incl - v;
 }
 
+// Add `v` to a counter that carries the call's tag above the bits of `mask`; returns the count before the add.  The place step
+// of the call before left the counter at (this call's tag | 0), so the add returns the place at once.  A counter with another
+// tag -- the first call on this memory, a layout that moved -- is taken over instead: look, then compare-and-swap to
+// (tag | v) or, once the tag is there, add.  (The blind add that found the wrong tag changed a word that held nothing of
+// value; the tag cannot change back during the launch, so an add after a matching look is safe, and a lost swap just looks
+// again: lock-free, and bounded all the same.)  `taken` is false when the take-over ran out of tries.
+__device__ __forceinline__ uint64_t tagged_add(uint64_t* word, uint64_t tag, uint64_t mask, uint64_t v, uint32_t spin_limit,
+                                               bool& taken) {
+  unsigned long long* ctr = reinterpret_cast<unsigned long long*>(word);
+  unsigned long long old = atomicAdd(ctr, (unsigned long long)v);
+  taken = true;
+  if ((old & ~mask) == tag) return old & mask;
+  for (uint32_t tries = 0; tries < spin_limit; ++tries) {
+    old = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((old & ~mask) == tag) return atomicAdd(ctr, (unsigned long long)v) & mask;
+    if (atomicCAS(ctr, old, tag | v) == old) return 0;   // the first of this call
+  }
+  taken = false;
+  return 0;
+}
+
 __global__ __launch_bounds__(kSortThreads) void fast3_decode_kernel(
     const int64_t* __restrict__ indices, const int64_t* __restrict__ rowidx,
     const int64_t* __restrict__ offsets, uint32_t nnz, uint32_t per_slice,
     const int32_t* __restrict__ nnz_dev, int64_t B, int D, float* __restrict__ zero_out, uint32_t sentinel,
     uint32_t p0, uint32_t p1, uint32_t p2, uint32_t shift, uint32_t ranges, GroupPlan plan) {
-  __shared__ uint32_t hist[kMaxRanges];
-  for (uint32_t i = threadIdx.x; i < ranges; i += kSortThreads) hist[i] = 0u;
-  const uint32_t epoch = (uint32_t)(plan.epochs[0] + 1ull);   // this call's number (nobody writes the word during this launch)
-  __syncthreads();
+  __shared__ uint32_t hist[kMaxRanges];    // ids of the round per range
+  __shared__ uint32_t place[kMaxRanges];   // the round's place inside the (range, bank) bucket (kNoBlock: it has none)
+  __shared__ uint32_t oslot[kMaxRanges];   // slot of the round's first overflow entry of the range (kNoBlock: none)
+  const uint64_t call = plan.epochs[0] + 1ull;   // this call's number (nobody writes the word during this launch)
+  const uint32_t epoch = (uint32_t)call;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    plan.epochs[1] = call;   // the running call's number, for the place step
+    *plan.ticket = 0u;       // the place step's workgroups draw their ranges from it (nobody reads it during this launch)
+  }
   // a piece of a larger call: positions pos0 ..., rows relative to the piece's first bag, its own share of the bags to clear
   const Piece* pc = plan.piece;
   const int64_t pos0 = pc ? pc->pos0 : 0, rowbase = pc ? pc->rowbase : 0;
@@ -352,12 +390,19 @@ __global__ __launch_bounds__(kSortThreads) void fast3_decode_kernel(
       }
   }
   const uint32_t s1 = s0 + per_slice < nnz ? s0 + per_slice : nnz;
-  constexpr int UD = 4;   // ids per thread whose loads are in flight together
-  for (uint32_t base = s0 + threadIdx.x; base < s1; base += kSortThreads * UD) {
+  const uint32_t bank = blockIdx.x % plan.banks, cap = plan.cap;
+  const uint64_t tag = counter_tag(call), otag = ovf_tag(call);
+  uint64_t* const rctr = plan.rcount + (size_t)bank * kMaxRanges;
+  uint2* const bkt = plan.bucket + (size_t)bank * cap;   // + range * banks * cap
+  const size_t rstride = (size_t)plan.banks * cap;
+  constexpr int UD = kRoundIds / kSortThreads;   // ids per thread, held in registers from their loads to their stores
+  for (uint32_t r0 = s0; r0 < s1; r0 += kRoundIds) {   // (one round unless the slice holds more than kRoundIds ids)
+    for (uint32_t i = threadIdx.x; i < ranges; i += kSortThreads) hist[i] = 0u;
+    __syncthreads();
     int64_t idv[UD], o0[UD], o1[UD], rv[UD];
 #pragma unroll
     for (int u = 0; u < UD; ++u) {
-      const uint32_t n = base + u * kSortThreads;
+      const uint32_t n = r0 + threadIdx.x + u * kSortThreads;
       const int64_t g = pos0 + n;   // position in the whole id list
       const bool on = n < s1 && (int64_t)n < cnt;
       idv[u] = on ? indices[g] : 0;
@@ -366,14 +411,13 @@ __global__ __launch_bounds__(kSortThreads) void fast3_decode_kernel(
       o0[u] = direct ? offsets[g] : -1;
       o1[u] = direct ? offsets[g + 1] : -1;
     }
+    uint32_t key[UD], val[UD], rng[UD], rank[UD];
 #pragma unroll
     for (int u = 0; u < UD; ++u) {
-      const uint32_t n = base + u * kSortThreads;
-      if (n >= s1) continue;
-      if ((int64_t)n >= cnt) {
-        plan.grp_in[n] = kNoGroup;
-        continue;
-      }
+      const uint32_t n = r0 + threadIdx.x + u * kSortThreads;
+      rng[u] = kNoGroup;
+      key[u] = val[u] = rank[u] = 0u;
+      if (n >= s1 || (int64_t)n >= cnt) continue;   // (ids past the live count are not grouped)
       int64_t id = idv[u];
       id = id < 0 ? 0 : (id >= (int64_t)sentinel ? (int64_t)sentinel - 1 : id);
       const int64_t g = pos0 + n;
@@ -400,122 +444,72 @@ __global__ __launch_bounds__(kSortThreads) void fast3_decode_kernel(
       const uint32_t rem = uu - i0 * (p1 * p2);
       const uint32_t i1 = rem / p2;
       const uint32_t group = i1 * p0 + i0;
-      plan.grp_in[n] = group;
-      plan.i2_in[n] = rem - i1 * p2;
-      plan.vals_in[n] = (uint32_t)row | (multi ? kMultiBit : 0u);
+      key[u] = (group & ((1u << shift) - 1u)) | ((rem - i1 * p2) << 16);   // (group inside the range < 4096, i2 < p2 <= 4096)
+      val[u] = (uint32_t)row | (multi ? kMultiBit : 0u);
+      rng[u] = group >> shift;
       plan.gstamp[group] = epoch;   // "this group holds an id" (every writer stores the same word)
-      atomicAdd(&hist[group >> shift], 1u);
+      rank[u] = atomicAdd(&hist[rng[u]], 1u);
     }
-  }
-  __syncthreads();
-  // this slice's place inside every range: arrival order of the slices, ONE returning atomic per slice and range on a
-  // counter tagged with the call's epoch.  The place step of the call before (same workspace layout) left every counter at
-  // (this call's tag | 0), so the add returns the place at once.  A counter with another tag -- the first call on this
-  // memory, a layout that moved -- is taken over instead: look, then compare-and-swap to (tag | own count) or, once the
-  // tag is there, add.  (The blind add that found the wrong tag changed a word that held nothing of value; the tag cannot
-  // change back during the launch, so an add after a matching look is safe, and a lost swap just looks again.)
-  const uint64_t tag = counter_tag(plan.epochs[0] + 1ull);
-  uint32_t* dst = plan.shist + (size_t)blockIdx.x * ranges;
-  for (uint32_t i = threadIdx.x; i < ranges; i += kSortThreads) {
-    unsigned long long* ctr = reinterpret_cast<unsigned long long*>(&plan.rcount[(blockIdx.x % kCountBanks) * kMaxRanges + i]);
-    unsigned long long old = atomicAdd(ctr, (unsigned long long)hist[i]);
-    uint32_t place = (uint32_t)(old & 0x3ffffffull);
-    if ((old & ~0x3ffffffull) != tag) {
-      place = 0;
-      bool taken = false;
-      for (uint32_t tries = 0; tries < plan.spin_limit; ++tries) {   // (ends after at most one round per slice of the bank; bounded all the same)
-        old = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((old & ~0x3ffffffull) == tag) {
-          place = (uint32_t)(atomicAdd(ctr, (unsigned long long)hist[i]) & 0x3ffffffull);
-          taken = true;
-          break;
-        }
-        if (atomicCAS(ctr, old, tag | hist[i]) == old) {
-          place = 0;   // the first slice of this call in the range
-          taken = true;
-          break;
+    __syncthreads();
+    // the round's place inside every (range, bank) bucket: arrival order of the rounds, ONE returning atomic per range the
+    // round holds ids of, on a counter tagged with the call's epoch
+    for (uint32_t i = threadIdx.x; i < ranges; i += kSortThreads) {
+      const uint32_t h = hist[i];
+      uint32_t at = 0u, os = kNoBlock;
+      if (h != 0u) {
+        bool taken;
+        at = (uint32_t)tagged_add(&rctr[i], tag, 0x3ffffffull, h, plan.spin_limit, taken);
+        if (!taken) {   // the round has no place: the plan is poisoned, its ids are not stored
+          report_fault(plan, p0 * p1, call, kFaultTakeOver);
+          at = kNoBlock;
+        } else if (at + h > cap) {
+          // the bucket is full: the excess goes to an overflow block {len, next} reserved with one atomic, pushed onto the
+          // range's list with one exchange (a head with another tag is an empty list: nothing is cleared between calls)
+          const uint32_t len = at >= cap ? h : at + h - cap;
+          const uint64_t b = tagged_add(plan.ovf_count, otag, kOvfMask, len + 1u, plan.spin_limit, taken);
+          if (!taken) {
+            report_fault(plan, p0 * p1, call, kFaultTakeOver);
+            at = kNoBlock;
+          } else if (b + 1u + len <= plan.ovf_slots) {   // (always: the area holds every id plus a header per (round, range))
+            const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long*>(&plan.ovf_head[i]), otag | b);
+            plan.ovf[b] = make_uint2(len, (old & ~kOvfMask) == otag ? (uint32_t)(old & kOvfMask) : kNoBlock);
+            os = (uint32_t)b + 1u;
+          } else {   // (cannot happen with a consistent layout: still never dropped ids in a plausible plan)
+            report_fault(plan, p0 * p1, call, kFaultOverflow);
+            at = kNoBlock;
+          }
         }
       }
-      if (!taken) report_fault(plan, p0 * p1, plan.epochs[0] + 1ull, kFaultTakeOver);   // the slice has no place: the plan is poisoned
+      place[i] = at;
+      oslot[i] = os;
     }
-    dst[i] = place;
-  }
-}
-
-// One slice of the spread step.  cursor[r] = ids of the ranges before r (a scan of the range counters the decode step left)
-// + this slice's place inside r.
-__device__ __forceinline__ void spread_slice(uint32_t s, uint32_t slices, uint32_t nnz, uint32_t per_slice, uint32_t shift,
-                                             uint32_t ranges, const GroupPlan& plan, uint32_t* cursor, uint32_t* wave_sums) {
-  // (every slice added to its bank's counter of every range -- zeros included -- so a bank that got a slice carries this
-  // call's tag; one that got none -- fewer slices than banks -- still holds the tag the place step before left, or anything:
-  // its count only counts under this call's tag)
-  uint32_t tot = 0, bef = 0;
-  if (threadIdx.x < ranges) {
-    const uint64_t tag = counter_tag(plan.epochs[0] + 1ull);
-    uint64_t w[kCountBanks];
+    __syncthreads();
+    // every id from its registers to its bucket entry -- or its overflow block
 #pragma unroll
-    for (int b = 0; b < kCountBanks; ++b) w[b] = plan.rcount[b * kMaxRanges + threadIdx.x];
-    bef = plan.shist[(size_t)s * ranges + threadIdx.x];
-#pragma unroll
-    for (int b = 0; b < kCountBanks; ++b) {
-      const uint32_t c = (w[b] & ~0x3ffffffull) == tag ? (uint32_t)(w[b] & 0x3ffffffull) : 0u;
-      tot += c;
-      if ((uint32_t)b < s % kCountBanks) bef += c;   // the banks before this slice's come first inside the range
+    for (int u = 0; u < UD; ++u) {
+      if (rng[u] == kNoGroup) continue;
+      const uint32_t at = place[rng[u]];
+      if (at == kNoBlock) continue;
+      const uint32_t p = at + rank[u];
+      if (p < cap) {
+        bkt[rng[u] * rstride + p] = make_uint2(val[u], key[u]);
+      } else {
+        const uint32_t os = oslot[rng[u]];
+        if (os != kNoBlock) plan.ovf[os + (p - (at > cap ? at : cap))] = make_uint2(val[u], key[u]);
+      }
     }
+    __syncthreads();   // (hist / place / oslot are the next round's)
   }
-  uint32_t all;
-  const uint32_t excl = block_exclusive<uint32_t, kSortThreads>(tot, wave_sums, all);
-  if (threadIdx.x < ranges) {
-    cursor[threadIdx.x] = excl + bef;
-    if (s == 0) plan.rstart[threadIdx.x] = excl;
-  }
-  if (s == 0 && threadIdx.x == 0) {
-    plan.rstart[ranges] = all;
-    plan.epochs[1] = plan.epochs[0] + 1ull;   // the running call's number, for the place step
-    *plan.ticket = 0u;                        // the place step's workgroups draw their ranges from it (nobody reads it during this launch)
-  }
-  __syncthreads();
-  const uint32_t s0 = s * per_slice;
-  const uint32_t s1 = s0 + per_slice < nnz ? s0 + per_slice : nnz;
-  for (uint32_t base = s0 + threadIdx.x; base < s1; base += kSortThreads * kSortBatch) {
-    uint32_t g[kSortBatch], i2v[kSortBatch], vv[kSortBatch];   // all loads of the batch first
-#pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      const uint32_t n = base + u * kSortThreads;
-      g[u] = n < s1 ? plan.grp_in[n] : kNoGroup;
-    }
-#pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      const uint32_t n = base + u * kSortThreads;
-      const bool on = g[u] != kNoGroup;
-      i2v[u] = on ? plan.i2_in[n] : 0u;
-      vv[u] = on ? plan.vals_in[n] : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      if (g[u] == kNoGroup) continue;
-      const uint32_t dst = atomicAdd(&cursor[g[u] >> shift], 1u);
-      if (dst >= nnz) continue;   // cannot happen with a consistent table; a bad counter must not become a wild store
-      plan.grp_mid[dst] = g[u];
-      plan.i2_mid[dst] = i2v[u];
-      plan.vals_mid[dst] = vv[u];
-    }
-  }
-}
-
-__global__ __launch_bounds__(kSortThreads) void fast3_spread_kernel(uint32_t nnz, uint32_t per_slice, uint32_t shift,
-                                                                   uint32_t ranges, GroupPlan plan) {
-  __shared__ uint32_t cursor[kMaxRanges];
-  __shared__ uint32_t wave_sums[kSortThreads / kWave];
-  spread_slice(blockIdx.x, gridDim.x, nnz, per_slice, shift, ranges, plan, cursor, wave_sums);
 }
 
 // The place step of one range: count, place and describe in ONE launch.
-//   1. LDS histogram of the range's ids over its groups, scan -> ids per group (plan.counts), first position / first
-//      chunk of every group INSIDE the range; the range's totals (chunks, non-empty groups) are PUBLISHED, tagged with the
-//      call's epoch, for the ranges after it;
-//   2. every id takes its final position with one returning LDS atomic (positions need nothing from other ranges: the
-//      range's first position is a column sum the spread step already formed);
+//   0. where the range's ids are: its count in every bank (the range counters, final since the decode launch ended) and the
+//      head of its overflow list; the range's first position is the sum of the counters of the ranges before it (one load
+//      per counter and thread, no wait: every counter is final);
+//   1. LDS histogram of the range's ids (bucket entries, then the blocks of its overflow list) over its groups, scan -> ids
+//      per group (plan.counts), first position / first chunk of every group INSIDE the range; the range's totals (chunks,
+//      non-empty groups) are PUBLISHED, tagged with the call's epoch, for the ranges after it;
+//   2. every id takes its final position with one returning LDS atomic (positions need nothing from other ranges);
 //   3. only now the workgroup looks back: it sums what the ranges before it published -- long done by then, the scatter
 //      of step 2 sits between a workgroup's own publication and its first look (a separate count launch in front of the
 //      place launch cost ~5 us + the launch gap; a look-back BEFORE the scatter waited for the slowest histogram);
@@ -527,12 +521,44 @@ __global__ __launch_bounds__(kSortThreads) void fast3_spread_kernel(uint32_t nnz
 // that rotates the ranges against the dispatch order expires there at once).  In the ID-ONLY HALF of a two-phase forward --
 // the launch the data-parallel step runs BESIDE its RCCL all-reduce kernel (TTDataParallel.step(overlap=True)), where CUs
 // are held by a kernel this library does not control -- the range is a TICKET the workgroup draws when it starts (one atomic
-// on a header word the spread step zeroed): it then waits only for workgroups that have started, whatever the dispatcher did
+// on a header word the decode step zeroed): it then waits only for workgroups that have started, whatever the dispatcher did
 // (rocPRIM's look-back scan draws its tile ids the same way).  The ticket is not free -- the ~270 atomics of a launch queue
 // up on one address: +3 us on the grouping pass at 409 600 ids, A/B in one call; requesting the likely range's bounds next to
 // the ticket instead of behind it changed nothing -- which is why the whole forward, whose launches share the GPU with nothing
 // of this process, does not pay it (-DTTEMB_PLACE_TICKET_ALWAYS does).  Either way the wait is bounded: one that runs out
 // poisons the plan and reports (report_fault) -- never a hung device, never a plausible wrong table.
+// Every id of a range, as a workgroup: f({value, key}) for the range's bucket entries (banks in order, kSortBatch loads in
+// flight per thread), then for the entries of the blocks of its overflow list.  `cum` = entries of the banks before b
+// (cum[kCountBanks]: all of them); `head` = first overflow block; a list is not followed past `nids` blocks (every block
+// holds an id) nor past the overflow area.
+template <typename F>
+__device__ __forceinline__ void visit_range(const GroupPlan& plan, uint32_t range, const uint32_t* cum, uint32_t head,
+                                            uint32_t nids, F&& f) {
+  const uint2* bk = plan.bucket + (size_t)range * plan.banks * plan.cap;
+  const uint32_t nb = cum[kCountBanks];
+  for (uint32_t k0 = threadIdx.x; k0 < nb; k0 += kRangeThreads * kSortBatch) {
+    uint2 e[kSortBatch];   // all loads of the batch first
+#pragma unroll
+    for (int u = 0; u < kSortBatch; ++u) {
+      const uint32_t k = k0 + u * kRangeThreads;
+      uint32_t b = 0;
+#pragma unroll
+      for (int j = 1; j < kCountBanks; ++j) b += k >= cum[j] ? 1u : 0u;   // the last bank whose entries start at or before k
+      e[u] = k < nb ? bk[(size_t)b * plan.cap + (k - cum[b])] : make_uint2(0u, kNoGroup);
+    }
+#pragma unroll
+    for (int u = 0; u < kSortBatch; ++u) f(e[u]);
+  }
+  uint32_t blk = head;   // (workgroup-uniform)
+  for (uint32_t hops = 0; blk != kNoBlock && hops < nids && blk < plan.ovf_slots; ++hops) {
+    const uint2 h = plan.ovf[blk];
+    const uint32_t len = h.x;
+    if ((uint64_t)blk + 1u + len > plan.ovf_slots) break;   // (never trust a table with an address)
+    for (uint32_t j = threadIdx.x; j < len; j += kRangeThreads) f(plan.ovf[blk + 1u + j]);
+    blk = h.y;
+  }
+}
+
 constexpr uint64_t kEpochMask = (1ull << 40) - 1ull;
 static_assert(kMaxRanges <= kRangeThreads, "the look-back reads one published word per thread");
 __device__ __forceinline__ void place_range(const uint32_t ranges, uint32_t G, uint32_t shift,
@@ -561,19 +587,47 @@ __device__ __forceinline__ void place_range(const uint32_t ranges, uint32_t G, u
     if (range >= ranges) return;   // (cannot happen: `ranges` workgroups draw from a counter that started at 0)
   }
   const uint32_t g0 = range << shift;
-  const uint32_t n0 = plan.rstart[range], n1 = plan.rstart[range + 1];
-  // ---- 1. histogram, scan, publication ----
-  for (uint32_t b0 = n0 + threadIdx.x; b0 < n1; b0 += kRangeThreads * kSortBatch) {
-    uint32_t g[kSortBatch];
+  // ---- 0. the range's ids per bank, its first position, its overflow list ----
+  __shared__ uint32_t rinfo[kCountBanks + 3];   // entries of the banks before b (+ all), first position, head of the list
+  {
+    const uint64_t ctag = counter_tag(plan.epochs[1]);
+    uint32_t c[kCountBanks], tot = 0u;
 #pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      const uint32_t n = b0 + u * kRangeThreads;
-      g[u] = n < n1 ? plan.grp_mid[n] - g0 : kNoGroup;
+    for (int b = 0; b < kCountBanks; ++b) {
+      const uint64_t w = threadIdx.x < ranges && (uint32_t)b < plan.banks ? plan.rcount[b * kMaxRanges + threadIdx.x] : 0ull;
+      c[b] = (w & ~0x3ffffffull) == ctag ? (uint32_t)(w & 0x3ffffffull) : 0u;   // (a bank no slice of this call used: 0)
+      tot += c[b];
     }
+    const uint64_t hw = threadIdx.x == 0 ? plan.ovf_head[range] : 0ull;
+    __syncthreads();   // (every thread has read its range from red, the scan's scratch)
+    uint64_t all;
+    const uint64_t excl = block_exclusive<uint64_t, kRangeThreads>(tot, red, all);
+    if (threadIdx.x == range) {
+      uint32_t acc = 0u;
 #pragma unroll
-    for (int u = 0; u < kSortBatch; ++u)
-      if (g[u] < span) atomicAdd(&gcount[g[u]], 1u);
+      for (int b = 0; b < kCountBanks; ++b) {
+        rinfo[b] = acc;
+        acc += c[b] < plan.cap ? c[b] : plan.cap;   // (the rest went to overflow blocks)
+      }
+      rinfo[kCountBanks] = acc;
+      rinfo[kCountBanks + 1] = (uint32_t)excl;
+    }
+    if (threadIdx.x == 0) {
+      const uint64_t otag = ovf_tag(plan.epochs[1]);
+      rinfo[kCountBanks + 2] = (hw & ~kOvfMask) == otag ? (uint32_t)(hw & kOvfMask) : kNoBlock;
+    }
+    __syncthreads();
   }
+  uint32_t cum[kCountBanks + 1];
+#pragma unroll
+  for (int b = 0; b <= kCountBanks; ++b) cum[b] = rinfo[b];
+  const uint32_t n0 = rinfo[kCountBanks + 1], head = rinfo[kCountBanks + 2];
+  const uint32_t nids = nnz;   // (bound of the list walk: a range holds at most the call's ids)
+  // ---- 1. histogram, scan, publication ----
+  visit_range(plan, range, cum, head, nids, [&](uint2 e) {
+    const uint32_t gl = e.y & 0xffffu;
+    if (gl < span) atomicAdd(&gcount[gl], 1u);   // (kNoGroup, or a word that is not of this range: never trust a table with an LDS address)
+  });
   __syncthreads();
   uint64_t carry = 0;
   uint32_t live_here = 0;
@@ -592,31 +646,21 @@ __device__ __forceinline__ void place_range(const uint32_t ranges, uint32_t G, u
     live_here += (uint32_t)__syncthreads_count(c != 0u);
   }
   const uint32_t chunks_here = (uint32_t)(carry >> 32);
+  const uint32_t n1 = n0 + (uint32_t)carry;   // (the range's ids: what its bucket and overflow blocks held)
   if (threadIdx.x == 0) {
     __hip_atomic_store(&plan.rpub[range], (epoch << 24) | (uint64_t)chunks_here, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&plan.rpub[ranges + range], (epoch << 24) | (uint64_t)live_here, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   // ---- 2. final positions ----
-  for (uint32_t b0 = n0 + threadIdx.x; b0 < n1; b0 += kRangeThreads * kSortBatch) {
-    uint32_t gl[kSortBatch], i2v[kSortBatch], vv[kSortBatch];   // all loads of the batch first
-#pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      const uint32_t n = b0 + u * kRangeThreads;
-      const bool on = n < n1;
-      gl[u] = on ? plan.grp_mid[n] - g0 : kNoGroup;
-      i2v[u] = on ? plan.i2_mid[n] : 0u;
-      vv[u] = on ? plan.vals_mid[n] : 0u;
-    }
-#pragma unroll
-    for (int u = 0; u < kSortBatch; ++u) {
-      if (gl[u] >= span) continue;   // (kNoGroup, or a word that is not of this range: never trust a table with an LDS address)
-      const uint32_t dst = atomicAdd(&cursor[gl[u]], 1u);
-      if (dst >= nnz) continue;   // as in the spread step: never trust a counter with an address
-      plan.i2s[dst] = i2v[u];
-      plan.vals[dst] = vv[u];
-    }
-  }
+  visit_range(plan, range, cum, head, nids, [&](uint2 e) {
+    const uint32_t gl = e.y & 0xffffu;
+    if (gl >= span) return;   // (as in step 1)
+    const uint32_t dst = atomicAdd(&cursor[gl], 1u);
+    if (dst >= nnz) return;   // never trust a counter with an address
+    plan.i2s[dst] = e.y >> 16;
+    plan.vals[dst] = e.x;
+  });
   // ---- 3. look back: chunks (and, for the last range, non-empty groups) of the ranges before this one ----
   uint64_t before = 0, live_before = 0;
   if (threadIdx.x < range) {
@@ -680,9 +724,15 @@ __device__ __forceinline__ void place_range(const uint32_t ranges, uint32_t G, u
       plan.counts[G] = (uint32_t)live_all + live_here;
     }
     if (range == 0) plan.epochs[0] = plan.epochs[1];   // the call is counted (nobody reads this word during this launch)
-    // this range's id counter, read for the last time by the spread step: left at (the NEXT call's tag | 0), so that
-    // the next decode step's first add already counts
-    for (int b = 0; b < kCountBanks; ++b) plan.rcount[b * kMaxRanges + range] = counter_tag(plan.epochs[1] + 1ull);
+  }
+  // The range counters, read for the last time in step 0 of every workgroup, are left at (the NEXT call's tag | 0), so that the
+  // next decode step's first add already counts -- by the last range's workgroup, after its look-back has seen every other
+  // workgroup publish, i.e. after every other workgroup's step 0.  The overflow counter likewise.
+  if (range == ranges - 1) {
+    const uint64_t next = counter_tag(plan.epochs[1] + 1ull);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)kCountBanks * ranges; i += kRangeThreads)
+      plan.rcount[(i / ranges) * kMaxRanges + i % ranges] = next;
+    if (threadIdx.x == 0) *plan.ovf_count = ovf_tag(plan.epochs[1] + 1ull);
   }
 }
 
@@ -780,9 +830,9 @@ __device__ __forceinline__ void prefix_unit(const float* __restrict__ G0, const 
   // any work at all?  (one lane per i0 of the slice)
   const uint32_t my = i0_begin + lane;
   // which groups hold an id: their counters when the grouping is complete (stamps == 0), else the stamps the decode step of
-  // this call left -- the unit then runs next to the spread step (1: the call's number is epochs[0] + 1, stable until the
-  // place step) or next to the place step (2: epochs[1], which the spread step wrote), before the counters exist
-  const uint32_t want = stamps == 0 ? 0u : (uint32_t)(stamps == 1 ? plan.epochs[0] + 1ull : plan.epochs[1]);
+  // this call left -- the unit then runs next to the place step (epochs[1], which the decode step wrote), before the counters
+  // exist
+  const uint32_t want = stamps == 0 ? 0u : (uint32_t)plan.epochs[1];
   const bool mine = lane < kPrefixGroups && my < i0_end &&
                     (stamps != 0 ? plan.gstamp[i1 * p0 + my] == want : plan.counts[i1 * p0 + my] != 0u);
   const unsigned long long live = __ballot(mine);
@@ -831,39 +881,12 @@ __global__ __launch_bounds__(64) void fast3_prefix_kernel(const float* __restric
   prefix_unit<Q0, Q1, Q2, R1, R2>(G0, G1, p0, plan, blockIdx.x, blockIdx.y, (int)threadIdx.x, (int)stamps);
 }
 
-// The prefix products ride in the spread AND the place launch, half of the units in each (they need the cores and the decode
-// step's stamps, nothing the grouping computes later): latency-bound kernels share the machine instead of queueing.  (All
-// of them next to the spread step: 17.7 us for a launch whose two halves take 11 and 8.6 us alone.)  At rank 32 a unit
-// keeps 64-80 registers of G1 row -- more than a 1024-thread workgroup has next to the spread step (q = 4,5,5 / 5,5,4 /
-// 4,4,8 spilled 20-72 bytes per lane there; q = 8,4,4, the papers100M shape, has room): those shapes put every unit into
-// the place launch (512-thread workgroups).
-template <int Q0, int Q1, int Q2, int R1, int R2>
-struct PrefixRides {
-  static constexpr bool value = R1 < 32 || Q0 >= 8;
-};
-
-template <int Q0, int Q1, int Q2, int R1, int R2>
-__global__ __launch_bounds__(kSortThreads) void fast3_spread_prefix_kernel(uint32_t slices, uint32_t nnz, uint32_t per_slice,
-                                                                          uint32_t shift, uint32_t ranges, uint32_t unit_end,
-                                                                          const float* __restrict__ G0,
-                                                                          const float* __restrict__ G1, uint32_t p0,
-                                                                          uint32_t p1, GroupPlan plan) {
-  __shared__ uint32_t cursor[kMaxRanges];
-  __shared__ uint32_t wave_sums[kSortThreads / kWave];
-  if (blockIdx.x < slices) {
-    spread_slice(blockIdx.x, slices, nnz, per_slice, shift, ranges, plan, cursor, wave_sums);
-    return;
-  }
-  const uint32_t blocks0 = (p0 + kPrefixGroups - 1) / kPrefixGroups;
-  const uint32_t unit = (blockIdx.x - slices) * (kSortThreads / kWave) + (threadIdx.x >> 6);
-  if (unit >= unit_end) return;
-  if constexpr (PrefixRides<Q0, Q1, Q2, R1, R2>::value)
-    prefix_unit<Q0, Q1, Q2, R1, R2>(G0, G1, p0, plan, unit % blocks0, unit / blocks0, (int)(threadIdx.x & 63), 1);
-}
-
+// The prefix products ride in the place launch, behind its range workgroups (they need the cores and the decode step's
+// stamps, nothing the grouping computes later): latency-bound kernels share the machine instead of queueing.  (Round 3 put a
+// quarter of them next to the spread step, a launch this pass no longer has.)
 template <int Q0, int Q1, int Q2, int R1, int R2>
 __global__ __launch_bounds__(kRangeThreads) void fast3_place_prefix_kernel(uint32_t ranges, uint32_t nnz, uint32_t max_chunks,
-                                                                          uint32_t G, uint32_t shift, uint32_t unit_begin,
+                                                                          uint32_t G, uint32_t shift,
                                                                           const float* __restrict__ G0,
                                                                           const float* __restrict__ G1, uint32_t p0,
                                                                           uint32_t p1, GroupPlan plan) {
@@ -874,9 +897,9 @@ __global__ __launch_bounds__(kRangeThreads) void fast3_place_prefix_kernel(uint3
     return;
   }
   const uint32_t blocks0 = (p0 + kPrefixGroups - 1) / kPrefixGroups;
-  const uint32_t unit = unit_begin + (blockIdx.x - ranges) * (kRangeThreads / kWave) + (threadIdx.x >> 6);
+  const uint32_t unit = (blockIdx.x - ranges) * (kRangeThreads / kWave) + (threadIdx.x >> 6);
   if (unit >= blocks0 * p1) return;
-  prefix_unit<Q0, Q1, Q2, R1, R2>(G0, G1, p0, plan, unit % blocks0, unit / blocks0, (int)(threadIdx.x & 63), 2);
+  prefix_unit<Q0, Q1, Q2, R1, R2>(G0, G1, p0, plan, unit % blocks0, unit / blocks0, (int)(threadIdx.x & 63), 1);
 }
 
 // ---------------------------------------------------------------------------------
@@ -3041,6 +3064,44 @@ static int sort_shift(int64_t G) {
   return shift;
 }
 static int sort_ranges(int64_t G) { const int sh = sort_shift(G); return (int)((G + (int64_t(1) << sh) - 1) >> sh); }
+// The buckets of the grouping pass fill the bytes the three-launch pass kept for its six id-sized tables, its [slices][ranges]
+// place table and its range starts: no size query changed.  Those bytes take, in this order, the overflow area for the worst
+// case (every id, plus one block header per (round of a slice, range) -- at most one per id), then the buckets: the rest,
+// ~16 bytes per id, split evenly over the (range, bank) pairs.  (The list heads sit in the workspace header.)  Uniform ids put nnz / (ranges * banks) ids
+// into each -- 187 at 409 600 ids on the products table (274 ranges, 8 banks) -- whose bucket then holds 361 (slack 1.9;
+// METIS-like frontiers, windows of 200 consecutive ids, come to a range in lumps of ~70 ids per group, which the slack mostly
+// absorbs).  A call of a handful of ids may get buckets of capacity 0: every id goes to overflow, still correct.
+struct GroupingLayout {
+  int slices, ranges, banks;
+  uint32_t per_slice;
+  int64_t bytes;             // all of it (a multiple of 256)
+  int64_t ovf_slots, cap;
+};
+static GroupingLayout grouping_layout(const DevShape& s, int64_t nnz) {
+  GroupingLayout L;
+  const int64_t G = num_groups(s);
+  L.slices = sort_slices(nnz);
+  L.ranges = sort_ranges(G);
+  L.banks = L.slices < kCountBanks ? L.slices : kCountBanks;
+  L.per_slice = (uint32_t)((nnz + L.slices - 1) / L.slices);
+  L.bytes = 6 * align256(nnz * 4) + align256((int64_t)L.slices * L.ranges * 4) + align256((int64_t)(L.ranges + 1) * 4);
+  const int64_t headers = (int64_t)L.slices * ((L.per_slice + kRoundIds - 1) / kRoundIds) * L.ranges;
+  L.ovf_slots = nnz + (headers < nnz ? headers : nnz);   // (<= 2 nnz: 4 of the 6 id tables)
+  const int64_t rest = L.bytes - align256(L.ovf_slots * 8);
+  L.cap = rest > 0 ? rest / ((int64_t)8 * L.ranges * L.banks) : 0;
+  return L;
+}
+// DIAGNOSTIC (ttemb_grouping_layout): {slices, ranges, banks, bucket capacity, overflow slots} of a grouping pass over nnz ids
+int fast3_grouping_layout(const DevShape& s, int64_t nnz, int64_t* out) {
+  if (!fast3_supported(s)) return fail(TTEMB_E_UNSUPPORTED, "no grouped kernels for this shape");
+  const GroupingLayout L = grouping_layout(s, nnz);
+  out[0] = L.slices;
+  out[1] = L.ranges;
+  out[2] = L.banks;
+  out[3] = L.cap;
+  out[4] = L.ovf_slots;
+  return TTEMB_OK;
+}
 
 // measured on the products shapes (tools/crossover.py, forward + dense backward): 4 096 ids 92 vs 107 us, 8 192 ids
 // 101 vs 197 us for the grouped path vs the wave-per-id kernels; the grouped path's fixed cost grows with the number
@@ -3284,21 +3345,16 @@ static int64_t carve_workspace(const DevShape& s, int64_t nnz, bool bwd, bool pl
     if (pl && p) carve_plan_part(s, nnz, p, pl);
   }
   if (need_grouping) {
-    uint32_t* in[6];
-    for (int i = 0; i < 6; ++i) in[i] = (uint32_t*)take(nnz * 4);
-    uint32_t* sh = (uint32_t*)take((int64_t)sort_slices(nnz) * sort_ranges(G) * 4);
-    uint32_t* rs = (uint32_t*)take((sort_ranges(G) + 1) * 4);
+    const GroupingLayout L = grouping_layout(s, nnz);
+    char* g = take(L.bytes);
     uint32_t* gs = (uint32_t*)take(G * 4);
-    uint64_t* rp = (uint64_t*)take(sort_ranges(G) * 16);
+    uint64_t* rp = (uint64_t*)take((int64_t)L.ranges * 16);
     if (pl) {
-      pl->grp_in = in[0];
-      pl->i2_in = in[1];
-      pl->vals_in = in[2];
-      pl->grp_mid = in[3];
-      pl->i2_mid = in[4];
-      pl->vals_mid = in[5];
-      pl->shist = sh;
-      pl->rstart = rs;
+      pl->ovf = (uint2*)g;
+      pl->bucket = g ? (uint2*)(g + align256(L.ovf_slots * 8)) : nullptr;
+      pl->cap = (uint32_t)L.cap;
+      pl->banks = (uint32_t)L.banks;
+      pl->ovf_slots = (uint32_t)L.ovf_slots;
       pl->gstamp = gs;
       pl->rpub = rp;
     }
@@ -3340,16 +3396,17 @@ int64_t fast3_workspace_bytes(const DevShape& s, int32_t op, int64_t nnz, int64_
 
 // fill plan->{i2s, vals, counts, gpre, ctab} from the ids
 static int run_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, hipStream_t st);
-static int run_spread_place_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int slices,
-                                   uint32_t per_slice, int ranges, int shift, hipStream_t st);
+static int run_place_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int ranges, int shift,
+                            hipStream_t st);
 
 static int group_ids(const DevShape& s, const CorePtrs& cores, const int64_t* indices, const int64_t* rowidx,
                      const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, float* zero_out,
                      bool with_prefix, GroupPlan* plan, hipStream_t st) {
   const int64_t G = num_groups(s);
   const uint32_t sentinel = (uint32_t)((unsigned long long)s.L[0] * s.p[0]);
-  const int slices = sort_slices(nnz), shift = sort_shift(G), ranges = sort_ranges(G);
-  const uint32_t per_slice = (uint32_t)((nnz + slices - 1) / slices);
+  const GroupingLayout L = grouping_layout(s, nnz);
+  const int slices = L.slices, shift = sort_shift(G), ranges = L.ranges;
+  const uint32_t per_slice = L.per_slice;
   const size_t span = (size_t)1 << shift;
   if (ranges > kMaxRanges || span * 16 > 64 * 1024) return fail(TTEMB_E_UNSUPPORTED, "too many (i0, i1) groups for the grouping pass");
   if (nnz >= (int64_t(1) << 26)) return fail(TTEMB_E_UNSUPPORTED, "too many ids for the grouping pass (26-bit range counters)");
@@ -3358,15 +3415,17 @@ static int group_ids(const DevShape& s, const CorePtrs& cores, const int64_t* in
                      (uint32_t)s.p[2], (uint32_t)shift, (uint32_t)ranges, *plan);
   int rc = check_hip(hipGetLastError(), "fast3_decode_kernel");
   if (rc) return rc;
-  if (with_prefix && !wide(s)) return run_spread_place_prefix(s, cores, *plan, nnz, slices, per_slice, ranges, shift, st);
-  hipLaunchKernelGGL(fast3_spread_kernel, dim3((unsigned)slices), dim3(kSortThreads), 0, st, (uint32_t)nnz, per_slice,
-                     (uint32_t)shift, (uint32_t)ranges, *plan);
-  rc = check_hip(hipGetLastError(), "fast3_spread_kernel");
-  if (rc) return rc;
+#ifndef TTEMB_PREFIX_APART   // (A/B: the prefix units as a launch of their own behind the place launch -- profiles/r08_grouping_buckets.txt)
+  if (with_prefix && !wide(s)) return run_place_prefix(s, cores, *plan, nnz, ranges, shift, st);
+#endif
   hipLaunchKernelGGL(fast3_place_kernel, dim3((unsigned)ranges), dim3(kRangeThreads), span * 16, st, (uint32_t)nnz,
                      (uint32_t)max_chunks(s, nnz), (uint32_t)G, (uint32_t)shift, *plan);
   rc = check_hip(hipGetLastError(), "fast3_place_kernel");
+#ifdef TTEMB_PREFIX_APART
+  if (rc == TTEMB_OK && with_prefix) rc = run_prefix(s, cores, *plan, st);
+#else
   if (rc == TTEMB_OK && with_prefix && wide(s)) rc = run_prefix(s, cores, *plan, st);   // wide ranks: the prefix products are a GEMM of their own
+#endif
   return rc;
 }
 
@@ -3388,12 +3447,16 @@ static int prepare(const DevShape& s, const CorePtrs& cores, bool bwd, const int
   plan->epochs = reinterpret_cast<uint64_t*>(header);
   plan->rcount = plan->epochs ? plan->epochs + 2 : nullptr;
   plan->ticket = header ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(header) + kHeaderPoisonOffset + 8) : nullptr;
+  plan->ovf_count = header ? reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(header) + kHeaderPoisonOffset + 16) : nullptr;
+  plan->ovf_head = header ? plan->ovf_count + 1 : nullptr;
 #ifdef TTEMB_PLACE_TICKET_ALWAYS
   plan->use_ticket = 1u;
 #else
   plan->use_ticket = plan_state == 1 ? 1u : 0u;   // (see place_range)
 #endif
-  static_assert(kHeaderPoisonOffset + 16 <= kFast3HeaderBytes, "the header holds the epoch words, every bank of range counters, the poison word and the ticket");
+  static_assert(kHeaderPoisonOffset + 24 + 8 * kMaxRanges <= kFast3HeaderBytes && kHeaderPoisonOffset % 8 == 0,
+                "the header holds the epoch words, every bank of range counters, the poison word, the ticket, the overflow counter "
+                "and the overflow list heads");
   const bool external = plan_buf != nullptr && plan_bytes >= fast3_plan_bytes(s, nnz);
 #ifdef TTEMB_KEEP_P_ALWAYS   // (A/B: the P table written by every forward)
   plan->keep_p = 1u;
@@ -3479,34 +3542,22 @@ static int run_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan&
   return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
 }
 
-// spread step + first half of the prefix units, then place step + the rest
+// place step + the prefix units (behind the range workgroups, one unit per wavefront)
 template <int Q0, int Q1, int Q2, int R1, int R2>
-static int run_spread_place_prefix_t(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int slices,
-                                     uint32_t per_slice, int ranges, int shift, hipStream_t st) {
+static int run_place_prefix_t(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int ranges, int shift,
+                              hipStream_t st) {
   const unsigned units = (unsigned)((s.p[0] + kPrefixGroups - 1) / kPrefixGroups) * (unsigned)s.p[1];
-  // A CU takes ONE 1024-thread workgroup at a time: a spread launch of more workgroups than CUs runs its surplus as a second
-  // round (split 50 %: 200 + 70 workgroups on 256 CUs, 17.3 us against 11.8 at 25 %).  A quarter of the units rides with the
-  // spread step -- what fits the CUs its slices leave free -- the rest with the place step (409 600 ids, spread + place:
-  // 25.6 / 25.2 / 30.1 / 30.0 / 29.6 us at 0 / 25 / 50 / 75 / 100 %; as launches of their own 10.7 + 11.2 + 8.8).
-  const unsigned per_a = kSortThreads / kWave, per_b = kRangeThreads / kWave;
-  const unsigned room = chain_cus() > slices ? (unsigned)(chain_cus() - slices) * per_a : 0u;
-  unsigned first = PrefixRides<Q0, Q1, Q2, R1, R2>::value ? units / 4 : 0u;
-  first = first > room ? room : first;
-  hipLaunchKernelGGL((fast3_spread_prefix_kernel<Q0, Q1, Q2, R1, R2>), dim3((unsigned)slices + (first + per_a - 1) / per_a),
-                     dim3(kSortThreads), 0, st, (uint32_t)slices, (uint32_t)nnz, per_slice, (uint32_t)shift, (uint32_t)ranges, first,
-                     cores.c[0], cores.c[1], (uint32_t)s.p[0], (uint32_t)s.p[1], plan);
-  int rc = check_hip(hipGetLastError(), "fast3_spread_prefix_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL((fast3_place_prefix_kernel<Q0, Q1, Q2, R1, R2>), dim3((unsigned)ranges + (units - first + per_b - 1) / per_b),
+  const unsigned per_b = kRangeThreads / kWave;
+  hipLaunchKernelGGL((fast3_place_prefix_kernel<Q0, Q1, Q2, R1, R2>), dim3((unsigned)ranges + (units + per_b - 1) / per_b),
                      dim3(kRangeThreads), ((size_t)16 << shift), st, (uint32_t)ranges, (uint32_t)nnz, (uint32_t)max_chunks(s, nnz),
-                     (uint32_t)num_groups(s), (uint32_t)shift, first, cores.c[0], cores.c[1], (uint32_t)s.p[0], (uint32_t)s.p[1], plan);
+                     (uint32_t)num_groups(s), (uint32_t)shift, cores.c[0], cores.c[1], (uint32_t)s.p[0], (uint32_t)s.p[1], plan);
   return check_hip(hipGetLastError(), "fast3_place_prefix_kernel");
 }
 
-static int run_spread_place_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int slices,
-                                   uint32_t per_slice, int ranges, int shift, hipStream_t st) {
+static int run_place_prefix(const DevShape& s, const CorePtrs& cores, const GroupPlan& plan, int64_t nnz, int ranges, int shift,
+                            hipStream_t st) {
   if (classify(s)) {
-#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_spread_place_prefix_t<a, b, c, d, e>(s, cores, plan, nnz, slices, per_slice, ranges, shift, st);
+#define TTEMB_X(a, b, c, d, e) if (shape_is(s, a, b, c, d, e)) return run_place_prefix_t<a, b, c, d, e>(s, cores, plan, nnz, ranges, shift, st);
     TTEMB_FAST3_SHAPES(TTEMB_X)
 #undef TTEMB_X
   }

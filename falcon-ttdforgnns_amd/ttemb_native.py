@@ -28,7 +28,7 @@ PATH_AUTO, PATH_GENERIC, PATH_FAST3, PATH_PER_BAG = 0, 1, 2, 3
 # every symbol include/ttemb.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
     "ttemb_abi_version", "ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_set_path",
-    "ttemb_profile_enable", "ttemb_profile_read", "ttemb_kernel_family", "ttemb_set_piece_limits", "ttemb_set_wide_slab_min_ids", "ttemb_init", "ttemb_status", "ttemb_set_spin_limit",
+    "ttemb_profile_enable", "ttemb_profile_read", "ttemb_kernel_family", "ttemb_set_piece_limits", "ttemb_set_wide_slab_min_ids", "ttemb_init", "ttemb_status", "ttemb_set_spin_limit", "ttemb_grouping_layout",
     "ttemb_forward", "ttemb_forward_group", "ttemb_forward_lookup", "ttemb_backward_dense", "ttemb_backward_sgd", "ttemb_backward_adagrad",
     "ttemb_window_workspace_bytes", "ttemb_forward_window", "ttemb_backward_dense_window", "ttemb_backward_sgd_window", "ttemb_backward_adagrad_window",
     "ttemb_sgd_step", "ttemb_sgd_step_guarded", "ttemb_adagrad_step", "ttemb_cache_update", "ttemb_cache_update_one_sweep", "ttemb_cache_populate",
@@ -84,6 +84,7 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_kernel_family.argtypes = [shp, i64, i64, i32]
     lib.ttemb_set_piece_limits.argtypes = [i64, i64]
     lib.ttemb_set_spin_limit.argtypes = [i64]
+    lib.ttemb_grouping_layout.argtypes = [shp, i64, ctypes.POINTER(ctypes.c_int64)]
     lib.ttemb_set_wide_slab_min_ids.argtypes = [i64]
     lib.ttemb_status.argtypes = []
     lib.ttemb_init.argtypes = []
@@ -311,6 +312,13 @@ def status() -> None:
     """Raise ``RuntimeError`` when a device-side wait of an earlier grouped lookup ran out (its results are NaN); consumes
     the fault.  The caller synchronises first when it wants the answer for everything it has enqueued."""
     _check(LIB.ttemb_status())
+
+
+def grouping_layout(shape: Shape, nnz: int) -> dict:
+    """DIAGNOSTIC: the grouped path's grouping layout for `nnz` ids (ttemb_grouping_layout)."""
+    out = (ctypes.c_int64 * 5)()
+    _check(LIB.ttemb_grouping_layout(ctypes.byref(shape), nnz, out))
+    return dict(zip(("slices", "ranges", "banks", "cap", "ovf_slots"), (int(x) for x in out)))
 
 
 def set_piece_limits(rows: int = 0, ids: int = 0) -> None:

@@ -146,6 +146,10 @@ int ttemb_init(void);
 #define TTEMB_HEADER_POISON_OFFSET 32784
 int ttemb_status(void);
 int ttemb_set_spin_limit(int64_t tries);
+/* DIAGNOSTIC (tests): the layout of the grouped path's id grouping pass for `nnz` ids on this table -- it launches nothing.
+ * out[5] = {slices of the id list, ranges of the group space, banks of range counters, entries per (range, bank) bucket,
+ * slots of the overflow area}.  TTEMB_E_UNSUPPORTED for a shape without grouped kernels. */
+int ttemb_grouping_layout(const ttemb_shape_t* shape, int64_t nnz, int64_t* out);
 
 /* Which kernels a lookup of `nnz` ids in `B` bags on this table would run, under the current ttemb_set_path: a
  * DIAGNOSTIC for tests, benchmarks and tuners (tuning_SAGE.py searches ranks in [2, 256]) -- it launches nothing.
