@@ -10,6 +10,7 @@ workload uses 409 600 = 2048 x 200 unique uniform ids, bag length 1, as DGL deli
 
   python bench.py --gpus 1 --steps 50 --warmup 10
   python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   (also writes the last timed step's outputs)
+  python bench.py --gpus 1 --steps 50 --warmup 10 --full               (also every other leg: roofline, CPU baselines, ...)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1 is data parallel (weak scaling): every rank looks up its own batch, the flattened
@@ -93,6 +94,10 @@ SHAPES = {   # name -> (p, q, ranks, num_embeddings)
 # 64 ... 256 -- ranks up to 32 run on the register-resident grouped chain, 64 and up on the wide-rank one (GEMM prefix,
 # per-group backward, GEMM dG1 / dG0)
 RANK_SWEEP = [([5, 5, 4], r) for r in (8, 16, 32, 64, 128, 256)] + [([4, 4, 8], r) for r in (64, 128, 256)]
+
+# the keys of the legs `--full` adds to the line (full_legs)
+FULL_LEGS = ("roofline", "cpu_baseline", "cpu_baseline_2048", "matrix", "papers_roofline", "rank_sweep", "batch2048_step",
+             "metis_like_step", "dp_mode_1gpu", "cache_on_step", "sage_epoch")
 
 
 def matrix_leg(nat, name, n_ids, dist_kind, iters=50):
@@ -294,9 +299,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--ids", type=int, default=409600, help="frontier ids per step per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the line reports (~45 s more): the roofline, the "
+                         "CPU baselines, the batch-2048, METIS-like, data-parallel and cache-on steps, the SAGE epoch, the "
+                         "matrix, the papers100M roofline and the rank sweep.  Without it those keys read null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the batch-2048 and METIS-like legs (keeps a rocprofv3 summary to the headline workload)")
+                    help="with --full: skip the legs on other workloads, keep the roofline and the CPU baselines "
+                         "(keeps a rocprofv3 summary to the headline workload)")
     ap.add_argument("--path", default="auto", choices=["auto", "generic", "fast3"])
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
@@ -433,6 +443,41 @@ def main():
                      "devices": torch.cuda.device_count(), "rehearsal_on_one_gpu": rehearsal}
     value = world * N * args.steps / elapsed
 
+    # everything else the line reports, after the timed steps; a plain run leaves it out (those keys read null)
+    legs = dict.fromkeys(FULL_LEGS)
+    if args.full:
+        legs = full_legs(args, nat, emb, step, fence, rng, id_sets, offsets, d_out, world, rank)
+
+    result = None
+    if rank == 0:
+        result = {
+            "metric": "tt_embedding_lookups_per_sec", "value": round(value, 1), "unit": "lookups/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "ms_per_step_gpu_events": round(gpu_ms / args.steps, 4), "step_gpu_ms": spread(step_gpu_ms),
+            "prewarm_s": round(prewarm_s, 3), "prewarm_steps": n_pw, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": "ogbn-products TTEmbeddingBag fwd+bwd+SGD per step, frontier of a "
+                                   "2048-seed batch = 409600 unique uniform ids per GPU, bag length 1",
+                       "p": P, "q": Q, "tt_ranks": RANKS, "num_embeddings": N_EMB, "ids_per_gpu_step": N,
+                       "parallelism": f"dp{world}", "kernel_path": args.path},
+            "dist": dist_info, "full": args.full, **legs,
+        }
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+    if rank == 0:
+        print(json.dumps(result))
+
+
+def full_legs(args, nat, emb, step, fence, rng, id_sets, offsets, d_out, world, rank):
+    """Everything `--full` adds to the line, run after the headline's timed steps: the roofline (ten more headline steps
+    with the library's kernel brackets on, and the chain timed at the C ABI), the CPU baselines and the legs on other
+    workloads.  Returns them under their keys in the line (None: a leg that --no-extras, --no-cpu-baseline or the world
+    size leaves out) on rank 0, {} on the other ranks."""
+    from FBTT.tt_embeddings_ops import TTEmbeddingBag
+    from ttemb_dist import TTDataParallel
+    N, n_sets = args.ids, len(id_sets)
     # roofline leg: kernels bracketed by HIP events on the stream they are launched on.
     # slot 0 = forward chain kernel, slot 2 = backward chunk kernel, slot 1 = all backward chain kernels,
     # slot 3 = grouping pass (counting sort + chunk table + prefix-product kernel).  Nominal work per
@@ -460,7 +505,7 @@ def main():
     nat.profile_enable(False)
     fence()
 
-    result = None
+    legs = {}
     if rank == 0:
         fwd, bwd, chunk = float(np.mean(fwd_ms)), float(np.mean(bwd_ms)), float(np.mean(chunk_ms))
         group = float(np.mean(group_ms))
@@ -763,25 +808,10 @@ def main():
                 sweep["q%s_r%d" % ("".join(str(x) for x in qs), r)] = matrix_leg(
                     nat, (SHAPES["products_r16"][0], qs, [r, r], N_EMB), 409600, "uniform", iters=10)
                 torch.cuda.empty_cache()
-        result = {
-            "metric": "tt_embedding_lookups_per_sec", "value": round(value, 1), "unit": "lookups/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_gpu_events": round(gpu_ms / args.steps, 4), "step_gpu_ms": spread(step_gpu_ms),
-            "prewarm_s": round(prewarm_s, 3), "prewarm_steps": n_pw, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "ogbn-products TTEmbeddingBag fwd+bwd+SGD per step, frontier of a "
-                                   "2048-seed batch = 409600 unique uniform ids per GPU, bag length 1",
-                       "p": P, "q": Q, "tt_ranks": RANKS, "num_embeddings": N_EMB, "ids_per_gpu_step": N,
-                       "parallelism": f"dp{world}", "kernel_path": args.path},
-            "dist": dist_info, "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_2048": cpu2048, "matrix": matrix, "papers_roofline": papers, "rank_sweep": sweep, "batch2048_step": small, "metis_like_step": local,
-            "dp_mode_1gpu": dp1, "cache_on_step": cached, "sage_epoch": epoch,
-        }
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(result))
+        legs = {"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_2048": cpu2048, "matrix": matrix,
+                "papers_roofline": papers, "rank_sweep": sweep, "batch2048_step": small, "metis_like_step": local,
+                "dp_mode_1gpu": dp1, "cache_on_step": cached, "sage_epoch": epoch}
+    return legs
 
 
 if __name__ == "__main__":

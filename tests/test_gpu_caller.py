@@ -285,14 +285,15 @@ def test_bench_two_ranks_as_a_fresh_child_process():
     """`python bench.py --gpus 2` the way the driver's scaling run starts it -- a fresh process that launches its own ranks
     through torch.distributed.run, rendezvous on 127.0.0.1, TTDataParallel.step(overlap=True) every step -- rehearsed on the
     one GPU of this box (TTEMB_BENCH_REHEARSAL=1: both ranks on GPU 0, gloo carries the all-reduce; RCCL needs a GPU per
-    rank).  Asserts the JSON line: two ranks, a per-rank time each, the weak-scaling value."""
+    rank).  Asserts the JSON line: two ranks, a per-rank time each, the weak-scaling value, and (`--full`) the roofline
+    leg's profiled steps, which contain the collective as well."""
     import json
     import subprocess
     env = dict(os.environ, TTEMB_BENCH_REHEARSAL="1", OMP_NUM_THREADS="4")
     env.pop("RANK", None)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box): tools/refresh_evidence.sh <tag>
 # Regenerates the evidence bench.py and profiles/README.md cite: PMC traffic + MFMA utilisation (counter-only passes),
-# the rocprofv3 --kernel-trace --stats summary of a short bench.py run, and the default bench.py line.
+# the rocprofv3 --kernel-trace --stats summary of a short bench.py --full run, and the default bench.py --full line.
 # Everything lands in gpurun_out/<tag>/ (copy what should be judged into profiles/).
 tag=${1:-evidence}
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -18,9 +18,9 @@ TRAFFIC_KBENCH_ARGS="--cfg papers --n 819200 --no-rowidx --plan" bash $R/tools/m
 cp $R/profiles/r05_papers_traffic.json $R/profiles/r05_papers_mfma_util.json $O/
 cp $(find $R/gpurun_out/pmc_mfma_t -name "*kernel_stats.csv" | head -1) $O/papers_kernel_stats.csv
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> $O/bench_profiled.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras > $O/bench_profiled.json 2> $O/bench_profiled.err || exit 1
 cp $O/prof/*/*kernel_stats.csv $O/bench_kernel_stats.csv
-cd $R && python3 bench.py > $O/bench_default.json 2> $O/bench_default.err || exit 1
+cd $R && python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err || exit 1
 # per-kernel summaries of the wide-rank chain (ranks 64 / 256 of the rank sweep), uniform and METIS-like ids
 bash $R/tools/prof_cfg.sh q554_r64 q554_r256 q448_r256 < /dev/null 2>&1 | grep -E "^==|uniform|calls" > $O/wide_kernels.txt || exit 1
 cd $R && for c in q554_r64 q554_r256; do python3 tools/kbench.py --cfg $c --iters 5 --no-rowidx --dist windows 2>/dev/null | tail -1 >> $O/wide_kernels.txt; done
