@@ -516,6 +516,29 @@ class _BagMean(torch.autograd.Function):
         return d_sums, None
 
 
+class _PadWeights(torch.autograd.Function):
+    """The masked-rows route of a padded call: ``w'[i] = keep[i] (w[i] or 1) (1 / len'(bag(i)) for a mean)``
+    (``ttemb_pad_weights``), the weights ``_WeightedBag`` then pools the bags-of-one rows with.  ``w`` is only given with
+    ``mode="sum"``, where ``w'`` is ``keep * w`` and its backward the same kernel on the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, weights: Optional[torch.Tensor], indices: torch.Tensor, offsets: torch.Tensor, pad: int,
+                mean: bool) -> torch.Tensor:
+        out = torch.empty(indices.numel(), dtype=torch.float32, device=indices.device)
+        _nat.pad_weights(indices, offsets, weights, pad, mean, out)
+        ctx.indices, ctx.offsets, ctx.pad = indices, offsets, pad
+        return out
+
+    @staticmethod
+    def backward(ctx, d_w: torch.Tensor):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        d_w = d_w.contiguous()
+        out = torch.empty_like(d_w)
+        _nat.pad_weights(ctx.indices, ctx.offsets, d_w, ctx.pad, False, out)
+        return out, None, None, None, None
+
+
 class _ReplayLookup(torch.autograd.Function):
     """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each."""
 
@@ -546,6 +569,7 @@ class CapturedLookup:
         assert module.sparse and module.num_tables == 1, "capture() covers the fused-optimiser mode of a single table"
         assert not (module.use_cache and not module.warmup), "capture() with a live row cache is not supported"
         assert module.mode == "sum", "capture() covers mode='sum' (unweighted)"
+        assert module.padding_idx is None, "capture() does not cover padding_idx: capture a module without it"
         self.module, self.nnz, self.B = module, int(nnz), int(B)
         dev = module.tt_cores[0].device
         self.indices = torch.zeros(self.nnz, dtype=torch.int64, device=dev)
@@ -630,6 +654,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     ``mode="sum"`` with ``w`` (float32 ``[nnz]``) pools ``w[i] * row(indices[i])``, ``mode="mean"`` divides each bag sum by
     the bag's length (an empty bag gives zeros).  Weights with ``mode="mean"`` raise ``ValueError``.  Gradients reach the
     cores through every optimiser mode, and ``w.grad`` when ``w`` requires it.
+
+    ``padding_idx`` (keyword-only; negative counts from the end) follows ``embedding_bag``'s: ids equal to it add nothing to
+    their bag, are not counted in a mean and send no gradient (``full_weight()[padding_idx]`` is not zero: a TT table has no
+    zero row).  ``forward(indices[rows, N])`` without offsets pools ``rows`` bags of N ids (``per_sample_weights`` then
+    ``[rows, N]``).  Routes: DESIGN.md §4.8.
     """
 
     __constants__ = ["num_tables", "num_embeddings", "embedding_dim", "tt_shape", "tt_rank"]
@@ -639,11 +668,18 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum") -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
+                 padding_idx: Optional[int] = None) -> None:
         super().__init__()
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         self.mode = mode
+        if padding_idx is not None:
+            if not -num_embeddings <= int(padding_idx) < num_embeddings:
+                raise ValueError(f"padding_idx must be in [-{num_embeddings}, {num_embeddings}), got {padding_idx}")
+            padding_idx = int(padding_idx) % num_embeddings
+        # ids equal to it are left out of their bags (a plain attribute: not part of the state dict)
+        self.padding_idx: Optional[int] = padding_idx
         # exact mode (``_ExactLookup``): True / False, or None = on for OptimType.EXACT_SGD and whenever
         # torch.are_deterministic_algorithms_enabled() at call time
         self.deterministic = deterministic
@@ -711,6 +747,8 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         self._dense_grad_out = None
         self._before_weights = None   # set by ttemb_dist.TTDataParallel while an update of the cores is pending
         self._use_windows = True      # num_tables > 1: per-table windows read on the device (False: always split on the host)
+        self._pad_partition = True    # padding_idx: drop the pad ids where the grouped kernels serve (False: masked rows only)
+        self._last_pad_route: Optional[str] = None   # route of the last padded call ("partition" / "masked")
         self._bucket_filled = False   # set by the backward when it wrote the core gradients into the wrapper's bucket
         self._family_cache: dict = {}  # (nnz, B, ...) -> "the backward of this size runs on the grouped kernels" (ttemb_dist)
         self._shape = _nat.make_shape(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks)
@@ -910,9 +948,106 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             out = torch.stack(outs, 0)
         return out.unsqueeze(0) if tables_dim and T == 1 else out
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True, *,
+    def _fixed_bags(self, indices: torch.Tensor, offsets: Optional[torch.Tensor], weights: Optional[torch.Tensor]):
+        """2-D ``indices[rows, N]`` without offsets: ``rows`` bags of N ids (for several tables, the num_tables * B bags
+        in table-major order) -> the flat ids, offsets 0, N, 2N, ... (module scratch on the device) and flat weights."""
+        if indices.dim() == 2:
+            if offsets is not None:
+                raise ValueError("offsets has to be None when indices is 2-D (bags of a fixed length)")
+            rows, N = indices.shape
+            if rows % self.num_tables != 0:
+                raise ValueError(f"2-D indices: {rows} rows are not num_tables ({self.num_tables}) * B bags")
+            if weights is not None and tuple(weights.shape) != (rows, N):
+                raise ValueError(f"per_sample_weights must have the shape of indices {[rows, N]}, got {list(weights.shape)}")
+            key = (rows, N, indices.device)
+            if getattr(self, "_fixed_key", None) != key:
+                self._fixed_offsets = torch.arange(rows + 1, dtype=torch.int64, device=indices.device) * N
+                self._fixed_key = key
+            return indices.reshape(-1), self._fixed_offsets, (None if weights is None else weights.reshape(-1))
+        if indices.dim() != 1:
+            raise ValueError(f"indices must be 1-D (with offsets) or 2-D (without), got {indices.dim()}-D")
+        if offsets is None:
+            raise ValueError("offsets is required when indices is 1-D")
+        return indices, offsets, weights
+
+    def _masked_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
+                          exact: bool) -> torch.Tensor:
+        """Masked-rows route of a padded call: one row per id (the lookup of bags of one, whichever bridge serves it), then
+        the bag sums with the weights of ``_PadWeights`` (0 for a pad id, 1 / len' for a mean)."""
+        w2 = _PadWeights.apply(weights, indices, offsets, self.padding_idx, self.mode == "mean")
+        nnz = indices.numel()
+        rows = self._lookup_one_table(table, nnz, indices, self._bags_of_one(nnz, indices.device), exact)
+        return _WeightedBag.apply(rows, w2, offsets, self)
+
+    def _pad_route(self, nnz: int, B: int, weighted: bool, exact: bool) -> str:
+        """"partition" (pad ids never reach the TT kernels) where the row-index lookup of this size runs on the grouped
+        kernels; else "masked" (see DESIGN §4.8)."""
+        if (weighted or exact or self.num_tables != 1 or (self.use_cache and not self.warmup) or nnz == 0 or B == 0
+                or not self._pad_partition):
+            return "masked"
+        key = (nnz, B, "pad", _nat.path_epoch)
+        route = self._family_cache.get(key)
+        if route is None:
+            if len(self._family_cache) > 256:
+                self._family_cache.clear()
+            fam = _nat.kernel_family(self._shape, nnz, B, False) & 7
+            route = self._family_cache[key] = ("partition" if fam in (_nat.FAMILY_GROUPED, _nat.FAMILY_GROUPED_WIDE)
+                                               else "masked")
+        return route
+
+    def _padded(self, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
+                tables_dim: bool) -> torch.Tensor:
+        """``forward`` with ``padding_idx`` set (1-D ids and their offsets by now)."""
+        if not indices.is_cuda:
+            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
+        if weights is not None:
+            if self.mode != "sum":
+                raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
+                                 "(as in torch.nn.functional.embedding_bag)")
+            _nat._check_weights(weights, indices.numel(), indices)
+            weights = weights.contiguous()
+        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
+        assert (offsets.numel() - 1) % self.num_tables == 0
+        T, B, nnz = self.num_tables, (offsets.numel() - 1) // self.num_tables, indices.numel()
+        dev = indices.device
+        if not self._fused_probe():
+            self.update_cache(indices)
+        exact = self._exact_active()
+        route = self._last_pad_route = self._pad_route(nnz, B, weights is not None, exact)
+        if route == "partition":
+            # pad ids never reach the TT kernels: the lookup runs on the kept ids and the compacted bags, the kept count
+            # stays on the device (the row-index form of the live cache)
+            ids = torch.empty_like(indices)
+            rows = torch.empty_like(indices)
+            offs = torch.empty(B + 1, dtype=torch.int64, device=dev)
+            kept = torch.empty(1, dtype=torch.int32, device=dev)
+            _nat.drop_padding(indices, offsets, self.padding_idx, ids, rows, offs, kept, self._ws)
+            out = TTLookupFunction.apply(self, 0, B, ids, rows, offs, kept, None, None, *self.tt_cores)
+            if self.mode == "mean":
+                out = _BagMean.apply(out, offs)
+        elif T == 1:
+            out = self._masked_one_table(0, indices, offsets, weights, exact)
+        elif B == 0:
+            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=dev)
+        else:
+            # several tables: the id list is split on the host (one synchronisation), as for weighted calls
+            bounds = offsets[:: B].tolist()
+            outs = []
+            for k in range(T):
+                lo, hi = int(bounds[k]), int(bounds[k + 1])
+                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
+                outs.append(self._masked_one_table(k, indices[lo:hi].contiguous(), offs_k,
+                                                   None if weights is None else weights[lo:hi], exact))
+            out = torch.stack(outs, 0)
+        return out.unsqueeze(0) if tables_dim and T == 1 else out
+
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # `warmup` is accepted and ignored, like the reference (it reads self.warmup, :862)
+        if offsets is None or indices.dim() != 1:
+            indices, offsets, per_sample_weights = self._fixed_bags(indices, offsets, per_sample_weights)
+        if self.padding_idx is not None:
+            return self._padded(indices, offsets, per_sample_weights, True)
         if per_sample_weights is not None or self.mode != "sum":
             return self._pooled(indices, offsets, per_sample_weights, True)
         if not indices.is_cuda:
@@ -953,15 +1088,21 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  optimizer: OptimType = OptimType.SGD, learning_rate: float = 0.1, eps: float = 1.0e-10,
                  sparse: bool = True, use_cache: bool = True, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
-                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum") -> None:
+                 batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
+                 padding_idx: Optional[int] = None) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
-                         enforce_embedding_dim, batch_count, deterministic=deterministic, mode=mode)
+                         enforce_embedding_dim, batch_count, deterministic=deterministic, mode=mode,
+                         padding_idx=padding_idx)
 
-    def forward(self, indices: torch.Tensor, offsets: torch.Tensor, warmup: bool = True, *,
+    def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         # same result as the reference's ``super().forward(...)[0]`` (:960-965) without the
         # [1, B, D] view: selecting table 0 would cost a zero-fill + copy of B*D floats in backward
+        if offsets is None or indices.dim() != 1:
+            indices, offsets, per_sample_weights = self._fixed_bags(indices, offsets, per_sample_weights)
+        if self.padding_idx is not None:
+            return self._padded(indices, offsets, per_sample_weights, False)
         if per_sample_weights is not None or self.mode != "sum":
             return self._pooled(indices, offsets, per_sample_weights, False)
         if not indices.is_cuda:

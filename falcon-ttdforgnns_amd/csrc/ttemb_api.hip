@@ -1358,6 +1358,26 @@ int ttemb_preprocess_update(const int64_t* indices, const int64_t* offsets, int6
                          cache_loc_out, nnz_tt_dev, dup_stamp, workspace, workspace_bytes, stream);
 }
 
+int64_t ttemb_drop_padding_workspace_bytes(int64_t nnz, int64_t B) {
+  if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "ttemb_drop_padding_workspace_bytes: negative size");
+  return kFast3HeaderBytes + drop_padding_workspace_bytes(nnz);
+}
+
+int ttemb_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B, int64_t pad,
+                       int64_t* indices_out, int64_t* rowidx_out, int64_t* offsets_out, int32_t* nnz_kept_dev, void* workspace,
+                       int64_t workspace_bytes, void* stream) {
+  ApiRange api_range("ttemb_drop_padding");
+  if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "ttemb_drop_padding: negative size");
+  if (nnz > 0x7fffffffll) return fail(TTEMB_E_BADARG, "ttemb_drop_padding: nnz exceeds int32 range");
+  if (!offsets || !offsets_out || !nnz_kept_dev || !workspace || (nnz > 0 && (!indices || !indices_out || !rowidx_out)))
+    return fail(TTEMB_E_BADARG, "ttemb_drop_padding: null buffer");
+  if (nnz > 0 && indices_out == indices) return fail(TTEMB_E_BADARG, "ttemb_drop_padding: the partition cannot run in place");
+  if (workspace_bytes < kFast3HeaderBytes) return fail(TTEMB_E_WORKSPACE, "ttemb_drop_padding: workspace smaller than its header");
+  return launch_drop_padding(indices, offsets, nnz, B, pad, indices_out, rowidx_out, offsets_out, nnz_kept_dev,
+                             reinterpret_cast<char*>(workspace) + kFast3HeaderBytes, workspace_bytes - kFast3HeaderBytes,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
 static int check_cache_args(const void* loc, const void* rowidx, int64_t start, int64_t nnz, int64_t D) {
   if (nnz < 0 || start < 0) return fail(TTEMB_E_BADARG, "negative size");
   if (D <= 0 || D % 4 != 0) return fail(TTEMB_E_BADARG, "embedding_dim %lld must be a positive multiple of 4", (long long)D);

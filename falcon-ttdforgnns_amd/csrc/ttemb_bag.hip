@@ -170,6 +170,39 @@ __global__ __launch_bounds__(kBagNT) void bag_mean_kernel(const float4* src, flo
   }
 }
 
+// Masked rows of a padded call: w_out[i] = keep[i] (w[i] or 1) (mean ? 1 / len'(bag(i)) : 1), keep[i] = indices[i] != pad,
+// len' = the kept ids of the bag.  One wavefront per bag (a count by ballots, then the stores); positions outside every bag
+// get 0.  A bag of no kept id gets zeros whatever its weights.
+__global__ __launch_bounds__(kBagNT) void pad_weights_kernel(const int64_t* __restrict__ indices, const int64_t* __restrict__ offsets,
+                                                             const float* __restrict__ w, int64_t nnz, int64_t B, int64_t pad,
+                                                             int mean, float* __restrict__ w_out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t per_block = kBagNT / kWave;
+  const int64_t stride = (int64_t)gridDim.x * per_block;
+  for (int64_t b = (int64_t)blockIdx.x * per_block + (threadIdx.x / kWave); b < B; b += stride) {
+    int64_t n0, n1;
+    bag_range(offsets, nnz, b, n0, n1);
+    float scale = 1.0f;
+    if (mean) {
+      int64_t kept = 0;
+      for (int64_t i0 = n0; i0 < n1; i0 += kWave) {
+        const int64_t i = i0 + lane;
+        kept += __popcll(__ballot(i < n1 && indices[i] != pad));
+      }
+      scale = kept > 0 ? 1.0f / (float)kept : 0.0f;
+    }
+    for (int64_t i = n0 + lane; i < n1; i += kWave)
+      w_out[i] = indices[i] != pad ? (w != nullptr ? w[i] * scale : scale) : 0.0f;
+  }
+  // positions before the first bag / after the last one
+  int64_t first = offsets[0], last = offsets[B];
+  first = first < 0 ? 0 : (first > nnz ? nnz : first);
+  last = last < first ? first : (last > nnz ? nnz : last);
+  const int64_t outside = first + (nnz - last);
+  for (int64_t j = (int64_t)blockIdx.x * kBagNT + threadIdx.x; j < outside; j += (int64_t)gridDim.x * kBagNT)
+    w_out[j < first ? j : last + (j - first)] = 0.0f;
+}
+
 int64_t chunks_of(int64_t nnz) { return (nnz + kBagChunk - 1) / kBagChunk; }
 
 unsigned grid_of(int64_t items, const Groups& gr) { return exact::ex_grid((items + gr.per_block - 1) / gr.per_block); }
@@ -258,6 +291,19 @@ int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t
   hipLaunchKernelGGL(bag_mean_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, reinterpret_cast<const float4*>(src),
                      reinterpret_cast<float4*>(dst), offsets, B, D / 4, gr.shift);
   return check_hip(hipGetLastError(), "bag_mean_kernel");
+}
+
+int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,
+                      int64_t pad, int32_t mean, float* weights_out, void* stream) {
+  if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "ttemb_pad_weights: negative nnz / B");
+  if (nnz == 0) return TTEMB_OK;
+  if (indices == nullptr || offsets == nullptr || weights_out == nullptr)
+    return fail(TTEMB_E_BADARG, "ttemb_pad_weights: indices / offsets / weights_out is null");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t per_block = kBagNT / kWave;
+  hipLaunchKernelGGL(pad_weights_kernel, dim3(exact::ex_grid((B + per_block - 1) / per_block)), dim3(kBagNT), 0, st, indices,
+                     offsets, weights, nnz, B, pad, mean != 0 ? 1 : 0, weights_out);
+  return check_hip(hipGetLastError(), "pad_weights_kernel");
 }
 
 }  // extern "C"

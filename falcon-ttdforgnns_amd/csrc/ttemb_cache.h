@@ -19,6 +19,11 @@ int launch_partition(const int64_t* indices, const int64_t* offsets, int64_t nnz
                      int64_t* hashtbl, int64_t* freq, const int32_t* state, int64_t H, int64_t* indices_out,
                      int64_t* rowidx_out, int32_t* loc_out, int32_t* nnz_tt_dev, int32_t* dup_stamp,
                      void* ws, int64_t ws_bytes, hipStream_t st);
+// ttemb_drop_padding: `ws` is the workspace behind its header
+int64_t drop_padding_workspace_bytes(int64_t nnz);
+int launch_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B, int64_t pad,
+                        int64_t* indices_out, int64_t* rowidx_out, int64_t* offsets_out, int32_t* nnz_kept_dev, void* ws,
+                        int64_t ws_bytes, hipStream_t st);
 int launch_cache_forward(const int32_t* loc, const int64_t* rowidx, const int64_t* offsets, int64_t start,
                          const int32_t* start_dev, int64_t nnz, const float* weight, int64_t D,
                          float* out, hipStream_t st);

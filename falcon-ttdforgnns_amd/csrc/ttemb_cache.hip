@@ -254,6 +254,49 @@ __global__ __launch_bounds__(kPartThreads) void cache_lookup_kernel(const int64_
   if (threadIdx.x == 0) blockcnt[blockIdx.x] = c;
 }
 
+// The rank core of the stable partitions (this one and ttemb_drop_padding's): the number of flagged positions before this
+// thread's, in the whole call -- the counts of the blocks before `block` (blockcnt, summed by wave 0: a few hundred
+// coalesced loads) plus a ballot rank inside the block.  No waits between workgroups.  `wave_cnt` / `wave_ball` / `before_lds`
+// are the caller's LDS (wave_ball may be null); `before_block` and `total` (flagged positions of this block) come back too.
+__device__ __forceinline__ int64_t partition_rank(const int32_t* __restrict__ blockcnt, int64_t block, bool f, int* wave_cnt,
+                                                  unsigned long long* wave_ball, int64_t* before_lds, int64_t& before_block,
+                                                  int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0) {
+    int64_t v = 0;
+    for (int64_t b0 = 0; b0 < block; b0 += 8 * kWave) {   // eight loads per lane in flight, then the sums
+      int32_t c[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int64_t b = b0 + k * kWave + lane;
+        c[k] = b < block ? blockcnt[b] : 0;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v += c[k];
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+      const uint32_t lo_w = __shfl_down((uint32_t)v, d, kWave), hi_w = __shfl_down((uint32_t)((uint64_t)v >> 32), d, kWave);
+      v += (int64_t)((uint64_t)lo_w | ((uint64_t)hi_w << 32));
+    }
+    if (lane == 0) *before_lds = v;
+  }
+  const unsigned long long ball = __ballot(f);
+  if (lane == 0) {
+    wave_cnt[wave] = __popcll(ball);
+    if (wave_ball != nullptr) wave_ball[wave] = ball;
+  }
+  __syncthreads();
+  before_block = *before_lds;
+  int64_t before = before_block + __popcll(ball & ((1ull << lane) - 1ull));
+  total = 0;
+  for (int w = 0; w < kPartThreads / kWave; ++w) {
+    if (w < wave) before += wave_cnt[w];
+    total += wave_cnt[w];
+  }
+  return before;
+}
+
 // selected (TT) items keep input order at the front; rejected (cached) items fill the
 // tail from the end backwards -- the order cub::DevicePartition::Flagged produces and
 // the reference's cache kernels therefore see (tt_embeddings_cuda.cu:1448-1490).
@@ -268,8 +311,7 @@ __global__ __launch_bounds__(kPartThreads) void partition_scatter_kernel(int64_t
                                                                          int32_t* __restrict__ nnz_tt,
                                                                          const int32_t* __restrict__ dup_stamp) {
   __shared__ int wave_cnt[kPartThreads / kWave];
-  __shared__ int64_t before_block;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ int64_t before_lds;
   const int64_t n = (int64_t)blockIdx.x * kPartThreads + threadIdx.x;
   int64_t id = 0, row = 0;
   int32_t where = 0;
@@ -281,36 +323,10 @@ __global__ __launch_bounds__(kPartThreads) void partition_scatter_kernel(int64_t
   // a cached id whose row's stamp is not its own position shares the row with another id of this call
   const bool dup = dup_stamp != nullptr && n < nnz && where >= 0 && dup_stamp[where] != (int32_t)n;
   const bool last = blockIdx.x == gridDim.x - 1;
-  if (wave == 0) {
-    int64_t v = 0;
-    const int64_t nb = (int64_t)blockIdx.x;
-    for (int64_t b0 = 0; b0 < nb; b0 += 8 * kWave) {   // eight loads per lane in flight, then the sums
-      int32_t c[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t b = b0 + k * kWave + lane;
-        c[k] = b < nb ? blockcnt[b] : 0;
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v += c[k];
-    }
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-      const uint32_t lo_w = __shfl_down((uint32_t)v, d, kWave), hi_w = __shfl_down((uint32_t)((uint64_t)v >> 32), d, kWave);
-      v += (int64_t)((uint64_t)lo_w | ((uint64_t)hi_w << 32));
-    }
-    if (lane == 0) before_block = v;
-  }
   const bool f = n < nnz && where < 0;
-  const unsigned long long ball = __ballot(f);
-  if (lane == 0) wave_cnt[wave] = __popcll(ball);
-  __syncthreads();
-  int64_t before = before_block + __popcll(ball & ((1ull << lane) - 1ull));
-  int total = 0;
-  for (int w = 0; w < kPartThreads / kWave; ++w) {
-    if (w < wave) before += wave_cnt[w];
-    total += wave_cnt[w];
-  }
+  int64_t before_block;
+  int total;
+  const int64_t before = partition_rank(blockcnt, (int64_t)blockIdx.x, f, wave_cnt, nullptr, &before_lds, before_block, total);
   if (last && threadIdx.x == 0) nnz_tt[0] = (int32_t)(before_block + total);
   if (dup) nnz_tt[1] = 1;   // (cleared by the lookup kernel; every writer stores the same word)
   if (n >= nnz) return;
@@ -370,6 +386,110 @@ int launch_partition(const int64_t* indices, const int64_t* offsets, int64_t nnz
                      blockcnt, indices, loc, indices_out, rowidx_out, loc_out, nnz_tt_dev, dup_stamp);
   profile_end(5, st);
   return check_hip(hipGetLastError(), "partition_scatter_kernel");
+}
+
+// ---------------------------------------------------------------------------------
+// drop padding (ttemb_drop_padding): the same stable partition with the flag "inside a bag and not the pad id" -- kept ids
+// at the front in input order, the others from the end backwards -- plus the compacted bag starts.  Integer work only, tiles
+// of kPartThreads positions in grid-stride loops (the grid honours ttemb_set_exact_grid), no waits between workgroups.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t clamp_pos(int64_t p, int64_t nnz) { return p < 0 ? 0 : (p > nnz ? nnz : p); }
+
+__device__ __forceinline__ bool pad_keep(int64_t id, int64_t n, int64_t nnz, int64_t first, int64_t last, int64_t pad) {
+  return n < nnz && n >= first && n < last && id != pad;
+}
+
+__global__ __launch_bounds__(kPartThreads) void pad_count_kernel(const int64_t* __restrict__ indices,
+                                                                 const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                 int64_t pad, int64_t tiles, int32_t* __restrict__ tilecnt) {
+  const int64_t first = offsets[0], last = offsets[B];
+  for (int64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+    const int64_t n = k * kPartThreads + threadIdx.x;
+    const int64_t id = n < nnz ? indices[n] : 0;
+    const int c = __syncthreads_count(pad_keep(id, n, nnz, first, last, pad));
+    if (threadIdx.x == 0) tilecnt[k] = c;
+  }
+}
+
+// offsets_out[b] = kept ids before clamp(offsets[b]): written by the tile that holds that position (the last tile also owns
+// position nnz), from the tile's prefix and its four wave ballots
+__global__ __launch_bounds__(kPartThreads) void pad_scatter_kernel(const int64_t* __restrict__ indices,
+                                                                   const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                   int64_t pad, int64_t tiles,
+                                                                   const int32_t* __restrict__ tilecnt,
+                                                                   int64_t* __restrict__ indices_out,
+                                                                   int64_t* __restrict__ rowidx_out,
+                                                                   int64_t* __restrict__ offsets_out,
+                                                                   int32_t* __restrict__ nnz_kept) {
+  __shared__ int wave_cnt[kPartThreads / kWave];
+  __shared__ unsigned long long wave_ball[kPartThreads / kWave];
+  __shared__ int64_t before_lds, bag_lo;
+  const int64_t first = offsets[0], last = offsets[B];
+  for (int64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+    const int64_t s = k * kPartThreads, n = s + threadIdx.x;
+    int64_t id = 0, row = 0;
+    if (n < nnz) {
+      id = indices[n];
+      if (n >= first && n < last) row = bag_of_position(offsets, B, n);
+    }
+    const bool keep = pad_keep(id, n, nnz, first, last, pad);
+    if (threadIdx.x == 0) {   // the first bag whose start lies in this tile or later
+      int64_t lo = 0, hi = B + 1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (clamp_pos(offsets[mid], nnz) < s) lo = mid + 1; else hi = mid;
+      }
+      bag_lo = lo;
+    }
+    int64_t before_block;
+    int total;
+    const int64_t before = partition_rank(tilecnt, k, keep, wave_cnt, wave_ball, &before_lds, before_block, total);
+    const bool last_tile = k == tiles - 1;
+    if (last_tile && threadIdx.x == 0) *nnz_kept = (int32_t)(before_block + total);
+    if (n < nnz) {
+      const int64_t dst = keep ? before : (nnz - 1 - (n - before));
+      indices_out[dst] = id;
+      rowidx_out[dst] = row;
+    }
+    const int64_t e = last_tile ? nnz + 1 : s + kPartThreads;
+    for (int64_t b = bag_lo + threadIdx.x; b <= B; b += kPartThreads) {
+      const int64_t p = clamp_pos(offsets[b], nnz);
+      if (p >= e) break;
+      int64_t kb = before_block;
+      const int64_t r = p - s;
+      if (r >= kPartThreads) {
+        kb += total;
+      } else {
+        const int w = (int)(r >> 6);
+        for (int v = 0; v < w; ++v) kb += wave_cnt[v];
+        kb += __popcll(wave_ball[w] & ((1ull << (r & 63)) - 1ull));
+      }
+      offsets_out[b] = kb;
+    }
+    __syncthreads();   // (this tile's LDS words are read above; the next tile rewrites them)
+  }
+}
+
+static int64_t pad_tiles(int64_t nnz) { return nnz > 0 ? (nnz + kPartThreads - 1) / kPartThreads : 1; }
+
+int64_t drop_padding_workspace_bytes(int64_t nnz) { return align256(pad_tiles(nnz) * 4); }
+
+int launch_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B, int64_t pad,
+                        int64_t* indices_out, int64_t* rowidx_out, int64_t* offsets_out, int32_t* nnz_kept_dev, void* ws,
+                        int64_t ws_bytes, hipStream_t st) {
+  const int64_t need = drop_padding_workspace_bytes(nnz);
+  if (need > ws_bytes)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_drop_padding needs %lld workspace bytes behind the header, got %lld",
+                (long long)need, (long long)ws_bytes);
+  int32_t* tilecnt = reinterpret_cast<int32_t*>(ws);
+  const int64_t tiles = pad_tiles(nnz);
+  const unsigned grid = exact::ex_grid(tiles);
+  hipLaunchKernelGGL(pad_count_kernel, dim3(grid), dim3(kPartThreads), 0, st, indices, offsets, nnz, B, pad, tiles, tilecnt);
+  int rc = check_hip(hipGetLastError(), "pad_count_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(pad_scatter_kernel, dim3(grid), dim3(kPartThreads), 0, st, indices, offsets, nnz, B, pad, tiles, tilecnt,
+                     indices_out, rowidx_out, offsets_out, nnz_kept_dev);
+  return check_hip(hipGetLastError(), "pad_scatter_kernel");
 }
 
 // ---------------------------------------------------------------------------------

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_set_exact_grid", "ttemb_forward_exact",
     "ttemb_backward_dense_exact", "ttemb_backward_sgd_exact", "ttemb_backward_adagrad_exact",
     "ttemb_bag_workspace_bytes", "ttemb_bag_reduce", "ttemb_bag_reduce_backward", "ttemb_bag_mean",
+    "ttemb_drop_padding_workspace_bytes", "ttemb_drop_padding", "ttemb_pad_weights",
 )
 
 
@@ -128,10 +129,15 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_bag_reduce.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
     lib.ttemb_bag_reduce_backward.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]
     lib.ttemb_bag_mean.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.ttemb_drop_padding_workspace_bytes.restype = i64
+    lib.ttemb_drop_padding_workspace_bytes.argtypes = [i64, i64]
+    lib.ttemb_drop_padding.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]
+    lib.ttemb_pad_weights.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
-                        "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes"):
+                        "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
+                        "ttemb_drop_padding_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -587,6 +593,41 @@ def bag_mean(src: torch.Tensor, dst: torch.Tensor, offsets: torch.Tensor) -> Non
     _check_sizes((src, dst), B * D)
     with _on_device(dst.device):
         _check(LIB.ttemb_bag_mean(_ptr(src), _ptr(dst), _ptr(offsets), B, D, _stream(dst)))
+
+
+def drop_padding_workspace_bytes(nnz: int, B: int) -> int:
+    key = ("pad", nnz, B)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_drop_padding_workspace_bytes(nnz, B))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def drop_padding(indices: torch.Tensor, offsets: torch.Tensor, pad: int, indices_out: torch.Tensor, rowidx_out: torch.Tensor,
+                 offsets_out: torch.Tensor, nnz_kept_dev: torch.Tensor, ws: Workspace) -> None:
+    """Stable partition of the ids into those != ``pad`` inside a bag (first, input order) and the rest; ``offsets_out`` the
+    compacted bags, ``nnz_kept_dev`` (int32[1]) their id count, on the device (``ttemb_drop_padding``)."""
+    nnz, B = indices.numel(), offsets.numel() - 1
+    if offsets_out.numel() != B + 1 or nnz_kept_dev.dtype != torch.int32 or nnz_kept_dev.numel() < 1:
+        raise ValueError("drop_padding: offsets_out must have B + 1 entries and nnz_kept_dev one int32")
+    dev = offsets.device
+    w = ws.get(drop_padding_workspace_bytes(nnz, B), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_drop_padding(_ptr(indices), _ptr(offsets), nnz, B, int(pad), _ptr(indices_out), _ptr(rowidx_out),
+                                      _ptr(offsets_out), _ptr(nnz_kept_dev), _ptr(w), w.numel(), _stream(offsets)))
+
+
+def pad_weights(indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor], pad: int, mean: bool,
+                weights_out: torch.Tensor) -> None:
+    """``weights_out[i] = (indices[i] != pad) * (weights[i] or 1) * (1 / kept ids of its bag if mean)`` (``ttemb_pad_weights``)."""
+    nnz = indices.numel()
+    _check_sizes((weights, weights_out), nnz)
+    with _on_device(weights_out.device):
+        _check(LIB.ttemb_pad_weights(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, offsets.numel() - 1, int(pad),
+                                     1 if mean else 0, _ptr(weights_out), _stream(weights_out)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

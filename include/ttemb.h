@@ -474,6 +474,29 @@ int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const
                               void* stream);
 int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t B, int64_t D, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Padding (torch.nn.functional.embedding_bag's padding_idx: an id equal to `pad` -- compared with the raw id, before any
+ * clamping of invalid ids -- adds nothing to its bag, is not counted in a mean and sends no gradient).  Two routes:
+ *   - ttemb_drop_padding: a stable flagged partition of indices[0:nnz].  The kept ids -- inside a bag of `offsets`
+ *     (int64[B+1]) and != pad -- come first in input order, rowidx_out[i] is the bag of kept id i, and the others fill the
+ *     tail from the end backwards (the order of ttemb_preprocess).  offsets_out[b] (int64[B+1]) = the kept ids before
+ *     offsets[b]: the compacted bags.  *nnz_kept_dev (int32) = the kept count, left on the device.  Then the lookup runs
+ *     on (indices_out, rowidx_out, offsets_out, nnz, nnz_kept_dev) -- pass offsets_out, never the original offsets: a bag
+ *     of one pad id has no writer -- and a mean divides by offsets_out's lengths.  Integer work only, no waits between
+ *     workgroups (deterministic by construction), grids capped by ttemb_set_exact_grid.  The workspace
+ *     (ttemb_drop_padding_workspace_bytes) is used behind the 40 KB header, so the lookups' workspace serves it.
+ *   - ttemb_pad_weights (the masked-rows route, with the bags-of-one lookup + ttemb_bag_reduce above):
+ *     weights_out[i] = keep[i] * (weights ? weights[i] : 1) * (mean ? 1 / len'(bag(i)) : 1), len' the kept ids of the bag
+ *     (0 for a bag without one); 0 for positions outside every bag.  weights may be NULL.  Deterministic likewise.
+ * No host synchronisation and no allocation.
+ * ------------------------------------------------------------------------------- */
+int64_t ttemb_drop_padding_workspace_bytes(int64_t nnz, int64_t B);
+int ttemb_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B, int64_t pad,
+                       int64_t* indices_out, int64_t* rowidx_out, int64_t* offsets_out, int32_t* nnz_kept_dev, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,
+                      int64_t pad, int32_t mean, float* weights_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
