@@ -386,3 +386,103 @@ def cache_backward_rowwise_adagrad(grad_output, cache_locations, rowidx, lr, eps
         mult = np.float32(lr) * np.float32(1.0 / (np.sqrt(old + gsq) + np.float32(eps)))
         w[loc] = w[loc] - g * mult
     return w, st
+
+
+# --------------------------------------------------------------------------
+# float64 reference with magnitudes (accuracy tests: tests/fp32_bound.py)
+# --------------------------------------------------------------------------
+def _id_factors(indices, offsets, weights, mode, pad):
+    """Per id: its bag, and the factor its row carries into the bag (weight, 1 / kept length of a mean bag, 0 for a pad)."""
+    indices = np.asarray(indices, dtype=np.int64)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    n = indices.shape[0]
+    rowidx = rowidx_from_offsets(offsets, n)
+    f = np.ones(n, dtype=np.float64) if weights is None else np.asarray(weights, dtype=np.float32).astype(np.float64)
+    keep = np.ones(n, dtype=bool) if pad is None else indices != int(pad)
+    f = np.where(keep, f, 0.0)
+    if mode == "mean":
+        kept = np.bincount(rowidx[keep], minlength=offsets.shape[0] - 1).astype(np.float64)
+        f = f / np.maximum(kept, 1.0)[rowidx]
+    else:
+        assert mode == "sum", mode
+    return rowidx, f, keep
+
+
+def _rows64(ii, cores, q, R, absolute):
+    """Forward partials v[t] ([n, Q_t, R_{t+1}], float64) of the rows of the ids only; |cores| when ``absolute``."""
+    T = len(cores)
+    n = ii[0].shape[0]
+    c = [np.abs(x).astype(np.float64) if absolute else np.asarray(x, dtype=np.float64) for x in cores]
+    v = [c[0][ii[0]].reshape(n, q[0], R[1])]
+    for t in range(1, T):
+        g = c[t][ii[t]].reshape(n, R[t], q[t] * R[t + 1])
+        v.append(np.matmul(v[-1], g).reshape(n, -1, R[t + 1]))
+    return v, c
+
+
+def tt_forward64(indices, offsets, cores, p_shapes, q_shapes, ranks, weights=None, mode="sum", pad=None):
+    """Bag lookup in float64 from the float32 inputs: ``(value, mag)``, both float64 [B, D].
+
+    ``mag`` is the same formula on |cores| and |weights|: per element, the sum of the magnitudes of its terms.  ``weights``
+    are per-id sample weights, ``mode`` "sum" or "mean" (divided by the bag's count of non-pad ids), ids equal to ``pad``
+    add nothing."""
+    T = len(p_shapes)
+    R = full_ranks(ranks, T)
+    q = [int(x) for x in q_shapes]
+    indices = np.asarray(indices, dtype=np.int64)
+    B = np.asarray(offsets).shape[0] - 1
+    D = int(np.prod(q))
+    val = np.zeros((B, D), dtype=np.float64)
+    mag = np.zeros((B, D), dtype=np.float64)
+    if indices.shape[0] == 0:
+        return val, mag
+    rowidx, f, _ = _id_factors(indices, offsets, weights, mode, pad)
+    ii = split_index(indices, p_shapes)
+    rv = _rows64(ii, cores, q, R, False)[0][-1].reshape(-1, D)
+    rm = _rows64(ii, cores, q, R, True)[0][-1].reshape(-1, D)
+    np.add.at(val, rowidx, f[:, None] * rv)
+    np.add.at(mag, rowidx, np.abs(f)[:, None] * rm)
+    return val, mag
+
+
+def _backward64(ii, rowidx, f, d_output, cores, q, R, absolute):
+    T = len(cores)
+    n = ii[0].shape[0]
+    v, c = _rows64(ii, cores, q, R, absolute)
+    dy = np.asarray(d_output, dtype=np.float32).astype(np.float64)
+    if absolute:
+        dy, f = np.abs(dy), np.abs(f)
+    grads = [np.zeros(x.shape, dtype=np.float64) for x in cores]
+    dv = f[:, None] * dy[rowidx]
+    for t in range(T - 1, 0, -1):
+        a = v[t - 1]
+        dc = dv.reshape(n, a.shape[1], q[t] * R[t + 1])
+        np.add.at(grads[t], ii[t], np.matmul(a.transpose(0, 2, 1), dc).reshape(n, -1))
+        g = c[t][ii[t]].reshape(n, R[t], q[t] * R[t + 1])
+        dv = np.matmul(dc, g.transpose(0, 2, 1))
+    np.add.at(grads[0], ii[0], dv.reshape(n, -1))
+    wg = np.einsum("nd,nd->n", dy[rowidx], v[-1].reshape(n, -1))
+    return grads, wg
+
+
+def tt_dense_backward64(indices, offsets, d_output, cores, p_shapes, q_shapes, ranks, weights=None, mode="sum", pad=None):
+    """Dense core gradients in float64: a list of ``(value, mag, n_ids)`` per core, ``n_ids[i]`` the number of non-pad ids
+    (with multiplicity) whose digit in that core is ``i``.  With ``weights``, a second value: ``(value, mag)`` of the
+    weights' gradient (0 for pad ids)."""
+    T = len(p_shapes)
+    R = full_ranks(ranks, T)
+    q = [int(x) for x in q_shapes]
+    indices = np.asarray(indices, dtype=np.int64)
+    n = indices.shape[0]
+    if n == 0:
+        out = [(np.zeros(c.shape), np.zeros(c.shape), np.zeros(c.shape[0], dtype=np.int64)) for c in cores]
+        return (out, (np.zeros(0), np.zeros(0))) if weights is not None else out
+    rowidx, f, keep = _id_factors(indices, offsets, weights, mode, pad)
+    ii = split_index(indices, p_shapes)
+    gv, wv = _backward64(ii, rowidx, f, d_output, cores, q, R, False)
+    gm, wm = _backward64(ii, rowidx, f, d_output, cores, q, R, True)
+    counts = [np.bincount(ii[t][keep], minlength=cores[t].shape[0]).astype(np.int64) for t in range(T)]
+    out = list(zip(gv, gm, counts))
+    if weights is None:
+        return out
+    return out, (np.where(keep, wv, 0.0), np.where(keep, wm, 0.0))

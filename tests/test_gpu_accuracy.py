@@ -1,0 +1,296 @@
+"""Every lookup route against the float64 oracle, element by element, with the fp32 rounding bound of tests/fp32_bound.py
+(depth taken from the kernel that ran).  Inputs where a per-element check matters: core rows scaled by 10^U(-3, 0) with
+mixed signs (and the module's uniform / approx-uniform initialisers), dY rows scaled per bag, weights with zeros and
+negative values, skewed ids (hot rows, rows touched once, rows not touched), bags of 0 / 1 / 2 / 3 / 7 ids and one of 600.
+Each case first asserts which route it takes, so that no case drifts onto another kernel silently."""
+import numpy as np
+import pytest
+import torch
+
+import fp32_bound as fb
+from oracle import tt_oracle as orc
+
+pytestmark = pytest.mark.gpu
+
+LR, EPS = 0.05, 1e-3
+WORST = {}   # route -> largest err / (u mag) seen (printed at the end of the module)
+
+
+@pytest.fixture(scope="module")
+def nat():
+    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
+    import ttemb_native
+    yield ttemb_native
+    ttemb_native.set_path(ttemb_native.PATH_AUTO)
+    ttemb_native.set_piece_limits(0, 0)
+    ttemb_native.set_wide_slab_min_ids(0)
+    for k in sorted(WORST):
+        print(f"\n  {k:28s} largest err/(u mag) {WORST[k]:.2f}", end="")
+
+
+def _dev(x):
+    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
+
+
+def _note(key, r):
+    WORST[key] = max(WORST.get(key, 0.0), r)
+
+
+def _route(fam, nat):
+    return {nat.FAMILY_SCALAR: "scalar", nat.FAMILY_PER_BAG: "per_bag", nat.FAMILY_PER_BAG_RT: "per_bag",
+            nat.FAMILY_GROUPED: "grouped", nat.FAMILY_GROUPED_WIDE: "wide"}[fam & 7]
+
+
+def _inputs(p, q, R, n_ids, seed, long_bag=600):
+    rng = np.random.default_rng(seed)
+    cores = fb.scaled_cores(rng, p, q, R)
+    ids, offs = fb.skewed_bags(rng, p, n_ids, long_bag)
+    dy = fb.scaled_dy(rng, offs.shape[0] - 1, int(np.prod(q)))
+    st0 = [(rng.random(c.shape) * 1e-6).astype(np.float32) for c in cores]
+    return cores, ids, offs, dy, st0
+
+
+def _check_all(key, route, p, q, R, Rk, cores, ids, offs, dy, st0, out, grads, sgd, ada, ada_st, merged=False, pieces=0):
+    """forward, dense gradients, fused SGD cores, fused Adagrad cores and state against the float64 oracle.  ``R`` is the
+    table's ranks (oracle), ``Rk`` the ranks the kernels ran (padded)."""
+    lens = np.diff(offs)
+    want, mag = orc.tt_forward64(ids, offs, cores, p, q, R)
+    _note(key, fb.assert_fp32_grade(out, want, mag, fb.bag_depth(route, Rk, lens, pieces=pieces), key + " forward", "bag"))
+    ref = orc.tt_dense_backward64(ids, offs, dy, cores, p, q, R)
+    for t, (v, m, n) in enumerate(ref):
+        depth = fb.grad_depth(route, q, Rk, t, n, merged=merged, pieces=pieces)
+        if grads is not None:
+            _note(key, fb.assert_fp32_grade(grads[t], v, m, depth, f"{key} dG{t}", "core row"))
+            fb.assert_untouched(grads[t], np.zeros_like(grads[t]), n, f"{key} dG{t}")
+        delta = fb.gamma(depth) * m
+        if sgd is not None:
+            _note(key, fb.assert_sgd_grade(sgd[t], cores[t], v, delta, LR, f"{key} SGD core {t}"))
+            fb.assert_untouched(sgd[t], cores[t], n, f"{key} SGD core {t}")
+        if ada is not None:
+            _note(key, fb.assert_adagrad_grade(ada[t], ada_st[t], cores[t], st0[t], v, delta, LR, EPS, f"{key} Adagrad core {t}"))
+            fb.assert_untouched(ada[t], cores[t], n, f"{key} Adagrad core {t}")
+            fb.assert_untouched(ada_st[t], st0[t], n, f"{key} Adagrad state {t}")
+
+
+def _abi_run(nat, p, q, R, cores, ids, offs, dy, st0, plan=False):
+    """forward, dense gradients, fused SGD and fused Adagrad through the C ABI (ids with their offsets, no row index)."""
+    shape, ws = nat.make_shape(p, q, R), nat.Workspace()
+    c = [_dev(x) for x in cores]
+    I, O, dY = _dev(ids), _dev(offs), _dev(dy)
+    B, nnz = offs.shape[0] - 1, ids.shape[0]
+    pl = nat.new_plan(shape, nnz, I.device) if plan else None
+    out = torch.full((B, int(np.prod(q))), float("nan"), device="cuda")
+    nat.forward(shape, c, I, None, O, nnz, None, B, out, ws, pl)
+    g = [torch.full_like(x, float("nan")) for x in c]
+    nat.backward_dense(shape, c, I, None, nnz, None, B, dY, g, ws, pl, O)
+    cs = [x.clone() for x in c]
+    nat.backward_sgd(shape, cs, I, None, nnz, None, B, dY, LR, ws, pl, O)
+    ca, st = [x.clone() for x in c], [_dev(s) for s in st0]
+    nat.backward_adagrad(shape, ca, st, I, None, nnz, None, B, dY, LR, EPS, ws, pl, O)
+    torch.cuda.synchronize()
+    h = lambda ts: [x.cpu().numpy() for x in ts]
+    return out.cpu().numpy(), h(g), h(cs), h(ca), h(st)
+
+
+# (key, p, q, inner ranks, ids, path, wanted family without route flags, route flag that must be set or None, kernel ranks)
+ABI_CASES = [
+    ("generic", [23, 290, 310], [4, 5, 5], [16, 16], 4000, "generic", 0, None, None),
+    ("small3", [23, 290, 310], [4, 5, 5], [16, 16], 2000, "auto", 1, None, None),
+    ("rt3", [23, 290, 310], [6, 4, 4], [16, 16], 2000, "auto", 2, None, None),
+    ("fast3", [8, 20, 3000], [4, 5, 5], [16, 16], 20000, "fast3", 3, None, None),
+    ("prefix_in_chain", [41, 50, 30], [4, 5, 5], [16, 16], 6000, "fast3", 3, "prefix", None),
+    ("group_products_in_chain", [41, 50, 30], [8, 4, 4], [32, 32], 6000, "fast3", 3, "group_products", None),
+    ("padded_12_to_16", [40, 50, 60], [4, 5, 5], [12, 12], 12000, "auto", 3 | 32, None, [16, 16]),
+    ("merged_2core", [7, 33], [16, 8], [16], 9000, "auto", 3 | 16, None, None),
+    ("merged_4core", [12, 9, 14, 11], [5, 5, 2, 2], [16, 16, 16], 15000, "fast3", 3 | 16, None, None),
+]
+
+
+@pytest.mark.parametrize("case", ABI_CASES, ids=[c[0] for c in ABI_CASES])
+def test_route_within_the_fp32_bound(nat, case):
+    key, p, q, r, n_ids, path, want_fam, flag, rk = case
+    R, Rk = [1] + r + [1], [1] + (rk or r) + [1]
+    nat.set_path({"auto": nat.PATH_AUTO, "generic": nat.PATH_GENERIC, "fast3": nat.PATH_FAST3}[path])
+    cores, ids, offs, dy, st0 = _inputs(p, q, R, n_ids, seed=len(key) + n_ids)
+    shape = nat.make_shape(p, q, R)
+    fam = nat.kernel_family(shape, ids.shape[0], offs.shape[0] - 1, True)
+    assert fam & ~nat.FAMILY_ROUTE_FLAGS == want_fam, (key, fam)
+    if flag == "prefix":
+        assert fam & nat.FAMILY_PREFIX_IN_CHAIN, (key, fam)
+    if flag == "group_products":
+        assert fam & nat.FAMILY_GROUP_PRODUCTS_IN_CHAIN, (key, fam)
+    res = _abi_run(nat, p, q, R, cores, ids, offs, dy, st0, plan=want_fam & 7 >= 3)
+    route = _route(fam, nat)
+    if len(p) != 3:   # a merged table: depths of the real chain, plus the split of the merged core's gradient
+        _check_all(key, route, p, q, R, Rk, cores, ids, offs, dy, st0, *res, merged=True)
+    else:
+        _check_all(key, route, p, q, R, Rk, cores, ids, offs, dy, st0, *res)
+
+
+@pytest.mark.parametrize("form", ["e_table", "lds_slabs"])
+@pytest.mark.parametrize("shape", [(5, 5, 4, 64, 64), (4, 4, 8, 256, 256)])
+def test_wide_rank_chain_within_the_fp32_bound(nat, shape, form):
+    q, R = list(shape[:3]), [1, shape[3], shape[4], 1]
+    p = [13, 50, 40]
+    nat.set_path(nat.PATH_FAST3)
+    nat.set_wide_slab_min_ids(1 if form == "lds_slabs" else 1 << 40)
+    cores, ids, offs, dy, st0 = _inputs(p, q, R, 3000, seed=sum(shape))
+    fam = nat.kernel_family(nat.make_shape(p, q, R), ids.shape[0], offs.shape[0] - 1, True)
+    assert fam & 7 == nat.FAMILY_GROUPED_WIDE, fam
+    res = _abi_run(nat, p, q, R, cores, ids, offs, dy, st0, plan=True)
+    _check_all(f"wide_r{shape[3]}_{form}", "wide", p, q, R, R, cores, ids, offs, dy, st0, *res)
+
+
+def test_call_in_pieces_within_the_fp32_bound(nat):
+    p, q, R = [30, 35, 400], [4, 5, 5], [1, 16, 16, 1]
+    nat.set_path(nat.PATH_FAST3)
+    cores, ids, offs, dy, st0 = _inputs(p, q, R, 12000, seed=17)
+    shape = nat.make_shape(p, q, R)
+    assert nat.plan_bytes(shape, ids.shape[0]) > 0
+    nat.set_piece_limits(900, 700)
+    assert nat.plan_bytes(shape, ids.shape[0]) == 0   # a call in pieces keeps no plan
+    assert nat.kernel_family(shape, ids.shape[0], offs.shape[0] - 1, True) & 7 == nat.FAMILY_GROUPED
+    B = offs.shape[0] - 1
+    pieces = -(-ids.shape[0] // 700) + -(-B // 900) + 1
+    res = _abi_run(nat, p, q, R, cores, ids, offs, dy, st0)
+    _check_all("pieces", "grouped", p, q, R, R, cores, ids, offs, dy, st0, *res, pieces=pieces)
+
+
+def test_three_table_windows_within_the_fp32_bound(nat):
+    p, q, R = [20, 25, 300], [4, 5, 5], [1, 16, 16, 1]
+    nat.set_path(nat.PATH_AUTO)
+    rng = np.random.default_rng(33)
+    T = 3
+    tabs = [fb.scaled_cores(rng, p, q, R) for _ in range(T)]
+    parts = [fb.skewed_bags(rng, p, 3000, long_bag=600 if k == 1 else 0) for k in range(T)]
+    B = max(o.shape[0] - 1 for _, o in parts)
+    ids, lens = [], []
+    for i, o in parts:   # every table B bags (the shorter lists padded with empty bags)
+        ids.append(i)
+        lens.append(np.concatenate([np.diff(o), np.zeros(B - (o.shape[0] - 1), dtype=np.int64)]))
+    ids = np.concatenate(ids)
+    offs = np.concatenate([[0], np.cumsum(np.concatenate(lens))]).astype(np.int64)
+    D = int(np.prod(q))
+    dy = fb.scaled_dy(rng, T * B, D)
+    shape, ws = nat.make_shape(p, q, R), nat.Workspace()
+    assert nat.window_workspace_bytes(shape, nat.OP_BACKWARD, ids.shape[0], T * B, B) > 0
+    I, O, dY = _dev(ids), _dev(offs), _dev(dy)
+    out = torch.full((T * B, D), float("nan"), device="cuda")
+    for k in range(T):
+        c = [_dev(x) for x in tabs[k]]
+        nat.forward_window(shape, c, I, O, k * B, B, out, ws)
+        g = [torch.full_like(x, float("nan")) for x in c]
+        nat.backward_window(shape, c, I, O, k * B, B, dY, ws, d_cores=g)
+        cs = [x.clone() for x in c]
+        nat.backward_window(shape, cs, I, O, k * B, B, dY, ws, lr=LR)
+        st0 = [(rng.random(x.shape) * 1e-6).astype(np.float32) for x in tabs[k]]
+        ca, st = [x.clone() for x in c], [_dev(s) for s in st0]
+        nat.backward_window(shape, ca, I, O, k * B, B, dY, ws, opt_state=st, lr=LR, eps=EPS)
+        torch.cuda.synchronize()
+        ids_k = ids[offs[k * B]:offs[(k + 1) * B]]
+        offs_k = offs[k * B:(k + 1) * B + 1] - offs[k * B]
+        fam = nat.kernel_family(shape, ids_k.shape[0], B, True)
+        h = lambda ts: [x.cpu().numpy() for x in ts]
+        _check_all("windows", _route(fam, nat) if fam & 7 >= 3 else "grouped", p, q, R, R, tabs[k], ids_k, offs_k,
+                   dy[k * B:(k + 1) * B], st0, out.cpu().numpy()[k * B:(k + 1) * B], h(g), h(cs), h(ca), h(st))
+
+
+def test_exact_mode_within_the_fp32_bound(nat):
+    p, q, R = [23, 290, 310], [4, 5, 5], [1, 16, 16, 1]
+    shape, ws = nat.make_shape(p, q, R), nat.Workspace()
+    assert nat.exact_unsupported_reason(shape) is None
+    cores, ids, offs, dy, st0 = _inputs(p, q, R, 8000, seed=5)
+    c = [_dev(x) for x in cores]
+    I, O, dY = _dev(ids), _dev(offs), _dev(dy)
+    B = offs.shape[0] - 1
+    out = torch.full((B, int(np.prod(q))), float("nan"), device="cuda")
+    nat.forward_exact(shape, c, I, O, B, out, ws)
+    g = [torch.full_like(x, float("nan")) for x in c]
+    nat.backward_exact(shape, c, I, O, B, dY, ws, d_cores=g)
+    cs = [x.clone() for x in c]
+    nat.backward_exact(shape, cs, I, O, B, dY, ws, lr=LR)
+    ca, st = [x.clone() for x in c], [_dev(s) for s in st0]
+    nat.backward_exact(shape, ca, I, O, B, dY, ws, opt_state=st, lr=LR, eps=EPS)
+    torch.cuda.synchronize()
+    h = lambda ts: [x.cpu().numpy() for x in ts]
+    _check_all("exact", "exact", p, q, R, R, cores, ids, offs, dy, st0, out.cpu().numpy(), h(g), h(cs), h(ca), h(st))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# through TTEmbeddingBag: weighted sum, mean, padding_idx (partition and zero-weight routes), 2-D bags, no_grad
+# ---------------------------------------------------------------------------------------------------------------------
+MODULE_CASES = [   # (key, p, q, inner ranks, ids, mode, weighted, init, padding route or None, 2-D bags)
+    ("weighted_sum_scaled", [23, 290, 310], [4, 5, 5], [16, 16], 8000, "sum", True, "scaled", None, False),
+    ("weighted_sum_uniform", [23, 290, 310], [4, 5, 5], [16, 16], 8000, "sum", True, "uniform", None, False),
+    ("mean_approx_uniform", [23, 290, 310], [4, 5, 5], [16, 16], 8000, "mean", False, "approx-uniform", None, False),
+    ("mean_pad_partition", [23, 290, 310], [4, 5, 5], [16, 16], 14000, "mean", False, "scaled", "partition", False),
+    ("sum_pad_zero_weight", [23, 290, 310], [4, 5, 5], [16, 16], 8000, "sum", False, "scaled", "masked", False),
+    ("weighted_pad", [23, 290, 310], [4, 5, 5], [16, 16], 3000, "sum", True, "scaled", "masked", False),
+    ("two_d_mean", [23, 290, 310], [4, 5, 5], [16, 16], 6000, "mean", False, "scaled", None, True),
+]
+
+
+@pytest.mark.parametrize("case", MODULE_CASES, ids=[c[0] for c in MODULE_CASES])
+def test_module_paths_within_the_fp32_bound(nat, case):
+    from FBTT import tt_embeddings_ops as ops
+    key, p, q, r, n_ids, mode, weighted, init, pad_route, two_d = case
+    R = [1] + r + [1]
+    nat.set_path(nat.PATH_AUTO)
+    rng = np.random.default_rng(len(key))
+    n_emb, D = int(np.prod(p)), int(np.prod(q))
+    if two_d:
+        ids = fb.skewed_bags(rng, p, n_ids, long_bag=0)[0]
+        L = 3
+        ids = ids[: (ids.shape[0] // L) * L]
+        offs = np.arange(0, ids.shape[0] + 1, L, dtype=np.int64)
+    else:
+        ids, offs = fb.skewed_bags(rng, p, n_ids)
+    pad = None
+    if pad_route is not None:
+        pad = int(ids[11])
+        ids[::13] = pad
+    torch.manual_seed(len(key))
+    emb = ops.TTEmbeddingBag(n_emb, D, r, p, q, sparse=False, use_cache=False, mode=mode, padding_idx=pad,
+                             weight_dist="uniform" if init == "scaled" else init)
+    if pad_route is not None:
+        emb._pad_partition = pad_route == "partition"
+    if init == "scaled":
+        with torch.no_grad():
+            for c, x in zip(emb.tt_cores, fb.scaled_cores(rng, p, q, R)):
+                c.copy_(_dev(x)[None])
+    cores = [c.detach()[0].cpu().numpy().copy() for c in emb.tt_cores]
+    w = fb.sample_weights(rng, ids.shape[0]) if weighted else None
+    B, nnz = offs.shape[0] - 1, ids.shape[0]
+    dy = fb.scaled_dy(rng, B, D)
+    I, O = _dev(ids), _dev(offs)
+    wt = _dev(w).requires_grad_(True) if weighted else None
+    fam = nat.kernel_family(emb._shape, nnz, nnz if weighted else B, True)
+    route = _route(fam, nat)
+    if two_d:
+        out = emb(I.view(-1, L), per_sample_weights=None)
+    else:
+        out = emb(I, O, per_sample_weights=wt)
+    if pad_route is not None:
+        assert emb._last_pad_route == pad_route, (key, emb._last_pad_route)
+    out.backward(_dev(dy))
+    torch.cuda.synchronize()
+    with torch.no_grad():   # the inference forward (no plan, no autograd node)
+        inf = (emb(I.view(-1, L)) if two_d else emb(I, O, per_sample_weights=wt.detach() if weighted else None)).cpu().numpy()
+    lens = np.diff(offs)
+    reduce = weighted or pad_route == "masked"
+    # (the pad routes look up the kept ids only, which may take another family: the larger depth of the two)
+    depth = np.maximum(fb.bag_depth(route, R, lens, reduce=reduce), fb.bag_depth("grouped", R, lens, reduce=reduce))
+    depth = depth + (2 if mode == "mean" else 0)
+    want, mag = orc.tt_forward64(ids, offs, cores, p, q, R, weights=w, mode=mode, pad=pad)
+    for got, what in ((out.detach().cpu().numpy(), "forward"), (inf, "no_grad forward")):
+        _note("module_" + key, fb.assert_fp32_grade(got, want, mag, depth, f"{key} {what}", "bag"))
+    ref = orc.tt_dense_backward64(ids, offs, dy, cores, p, q, R, weights=w, mode=mode, pad=pad)
+    if weighted:
+        ref, (wv, wm) = ref
+        _note("module_" + key, fb.assert_fp32_grade(wt.grad.cpu().numpy(), wv, wm, fb.wgrad_depth(route, q, R),
+                                                    f"{key} w.grad", "id"))
+    for t, ((v, m, n), c) in enumerate(zip(ref, emb.tt_cores)):
+        g = c.grad[0].cpu().numpy()
+        depth = np.maximum(fb.grad_depth(route, q, R, t, n, scaled=True), fb.grad_depth("grouped", q, R, t, n, scaled=True))
+        _note("module_" + key, fb.assert_fp32_grade(g, v, m, depth, f"{key} dG{t}", "core row"))
+        fb.assert_untouched(g, np.zeros_like(g), n, f"{key} dG{t}")
