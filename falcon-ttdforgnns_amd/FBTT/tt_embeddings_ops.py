@@ -36,9 +36,15 @@ _LOG = logging.getLogger(__name__)
 @unique
 class OptimType(Enum):
     """Optimiser selector; value strings match the reference (tt_embeddings_ops.py:18-33).
-    SGD / EXACT_SGD run the fused in-backward SGD; everything else runs fused Adagrad,
-    exactly as the reference dispatches (:229-286).  EXACT_SGD also turns on exact mode, the reference's documented
-    meaning ("deterministic updates (via sorting + segment reduction)", :20-23): see ``_ExactLookup``."""
+    SGD / EXACT_SGD run the fused in-backward SGD; ADAM runs the fused Adam / AdamW step (below); everything else runs
+    fused Adagrad, as the reference dispatches (:229-286).  EXACT_SGD also turns on exact mode, the reference's documented
+    meaning ("deterministic updates (via sorting + segment reduction)", :20-23): see ``_ExactLookup``.
+
+    ADAM (the reference has the member and runs Adagrad for it) is DENSE Adam, ``torch.optim.Adam`` /
+    ``torch.optim.AdamW`` (``decoupled_weight_decay=True``) on the dense core gradients, without amsgrad: every element of
+    every core moves on every applied step, also rows no id of the call touches -- the "untouched rows stay bit-identical"
+    property of fused SGD / Adagrad does not hold for it.  The step count lives on the device (``adam_step``); a call
+    without ids is a no-op that does not advance it.  DESIGN.md §4.9."""
     SGD = "sgd"
     EXACT_SGD = "exact_sgd"
     LAMB = "lamb"
@@ -54,6 +60,18 @@ class OptimType(Enum):
 
 
 _SGD_LIKE = (OptimType.SGD, OptimType.EXACT_SGD)
+
+
+def _step_call(m: "TableBatchedTTEmbeddingBag", table: int = 0):
+    """(state, adam) of a fused backward on table ``table``: ``state`` is None for SGD, the Adagrad state or Adam's first
+    moment; ``adam`` is None or (second moment, the table's device step words, hyper-parameters)."""
+    if m.optimizer in _SGD_LIKE:
+        return None, None
+    state = _nat.core_ptrs(m._states(), table)
+    if m.optimizer != OptimType.ADAM:
+        return state, None
+    v, step0, hp = m._adam_lean()
+    return state, (_nat.core_ptrs(v, table), step0 if table == 0 else m.adam_step[table], hp)
 
 
 class BufferList(nn.Module):
@@ -249,6 +267,10 @@ class TTLookupFunction(torch.autograd.Function):
                     _nat.cache_backward_sgd(cache_loc, rowidx, 0, nnz_dev, nnz, d_output,
                                             float(m.learning_rate), m.cache_weight.data,
                                             nnz_dev[1:] if nnz_dev.numel() > 1 else None)
+            elif m.optimizer == OptimType.ADAM:   # (never with a live cache: the constructor refuses that combination)
+                state, adam = _step_call(m, table)
+                _nat.backward_adam(m._shape, cores, state, adam[0], adam[1], indices, rowidx, nnz, nnz_dev, B, d_output,
+                                   adam[2], m._ws, ctx.plan, offsets)
             else:
                 state = _nat.core_ptrs(list(m.optimizer_state), table)
                 _nat.backward_adagrad(m._shape, cores, state, indices, rowidx, nnz, nnz_dev, B, d_output,
@@ -330,9 +352,9 @@ class _TablesLookup(torch.autograd.Function):
         T = m.num_tables
         if m.sparse:
             for k in range(T):
-                state = None if m.optimizer in _SGD_LIKE else _nat.core_ptrs(list(m.optimizer_state), k)
+                state, adam = _step_call(m, k)   # (Adam: one step count per table, advanced by that table's window)
                 _nat.backward_window(m._shape, _nat.core_ptrs(m.tt_cores, k), indices, offsets, k * B, B, d_output, m._ws,
-                                     opt_state=state, lr=float(m.learning_rate), eps=float(m.eps))
+                                     opt_state=state, lr=float(m.learning_rate), eps=float(m.eps), adam=adam)
             return (None,) * (4 + len(m.tt_cores))
         grads = [torch.empty_like(c) for c in m.tt_cores]
         for k in range(T):
@@ -363,7 +385,7 @@ class _SparseLookup(torch.autograd.Function):
             d_output = d_output.contiguous().float()
         state = None if m.optimizer in _SGD_LIKE else m._states()
         m._lean.backward(m._cores(), state, ctx.indices, ctx.offsets, ctx.indices.numel(), ctx.B, d_output,
-                         float(m.learning_rate), float(m.eps), ctx.plan)
+                         float(m.learning_rate), float(m.eps), ctx.plan, m._adam_lean())
         return None, None, None, None, None
 
 
@@ -412,7 +434,8 @@ class _BucketLookup(torch.autograd.Function):
 class _ExactLookup(torch.autograd.Function):
     """Exact mode: one table's lookup on the bit-reproducible kernels (``ttemb_forward_exact`` / ``ttemb_backward_*_exact``,
     include/ttemb.h "Exact mode").  Outputs, gradients, updated cores and optimizer state are a function of the inputs
-    only.  Fused SGD / Adagrad (``sparse``) update the touched rows only; dense gradients go to autograd, or into the
+    only.  Fused SGD / Adagrad (``sparse``) update the touched rows only, fused Adam every row (the exact dense gradient into
+    scratch, then the elementwise step); dense gradients go to autograd, or into the
     ``_dense_grad_out`` bucket of ``ttemb_dist.TTDataParallel`` (adding to it after the first backward of a step, like the
     plain lookup).  A module with several tables runs one exact call per table on the host-split id list."""
 
@@ -434,9 +457,9 @@ class _ExactLookup(torch.autograd.Function):
         cores = _nat.core_ptrs(m.tt_cores, table)
         n_fixed = 5
         if m.sparse:
-            state = None if m.optimizer in _SGD_LIKE else _nat.core_ptrs(list(m.optimizer_state), table)
+            state, adam = _step_call(m, table)
             _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, opt_state=state,
-                                lr=float(m.learning_rate), eps=float(m.eps))
+                                lr=float(m.learning_rate), eps=float(m.eps), adam=adam)
             return (None,) * (n_fixed + len(m.tt_cores))
         m._last_bwd_grouped = False   # no bounded device-side waits: nothing in the workspace header to look at
         bucket = getattr(m, "_dense_grad_out", None)
@@ -581,6 +604,9 @@ class CapturedLookup:
         cores = module._cores()
         state = None if module.optimizer in _SGD_LIKE else module._states()
         lr, eps = float(module.learning_rate), float(module.eps)
+        # Adam: b1, b2 and the weight decay are baked like lr / eps; the step count is a device word the graph advances
+        adam = module._adam_lean()
+        self._adam_key = module._adam_key()
         self.exact = module._exact_active()   # exact mode: the graphs hold the exact kernels
         if self.exact:
             self.plan = None
@@ -591,13 +617,21 @@ class CapturedLookup:
 
             def bwd():
                 _nat.backward_exact(module._shape, _nat.core_ptrs(cores), self.indices, self.offsets, self.B, self.d_output,
-                                    self._lean.ws, opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps)
+                                    self._lean.ws, opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps,
+                                    adam=None if adam is None else (_nat.core_ptrs(adam[0]), adam[1], adam[2]))
         else:
             def fwd():
                 self.plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output)
 
             def bwd():
-                self._lean.backward(cores, state, self.indices, self.offsets, self.nnz, self.B, self.d_output, lr, eps, self.plan)
+                self._lean.backward(cores, state, self.indices, self.offsets, self.nnz, self.B, self.d_output, lr, eps, self.plan,
+                                    adam)
+        # Capturing EXECUTES one backward on a zero gradient.  For SGD / Adagrad that leaves everything as it is; an Adam step
+        # on g = 0 advances t, decays m and v and, with weight decay, moves the cores: all of it is put back after the
+        # capture, so that a captured module equals an eager one step for step.
+        saved = None
+        if adam is not None:
+            saved = [t.detach().clone() for t in (*cores, *state, *adam[0], module.adam_step)]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):   # warm-up outside capture: workspace allocation, LDS-size attributes, size queries
@@ -610,6 +644,10 @@ class CapturedLookup:
             fwd()
         with torch.cuda.graph(self.bwd_graph):   # (a zero gradient: the captured update leaves the cores as they are)
             bwd()
+        if saved is not None:
+            with torch.no_grad():
+                for t, t0 in zip((*cores, *state, *adam[0], module.adam_step), saved):
+                    t.copy_(t0)
         self._lr, self._eps = lr, eps
         self._baked = self._pointers()
 
@@ -619,6 +657,8 @@ class CapturedLookup:
         ptrs = tuple(c.data_ptr() for c in m._cores())
         if m.optimizer not in _SGD_LIKE:
             ptrs += tuple(st.data_ptr() for st in m._states())
+        if m.optimizer == OptimType.ADAM:
+            ptrs += tuple(st.data_ptr() for st in m.optimizer_state_v) + (m.adam_step.data_ptr(),)
         return ptrs
 
     def __call__(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -627,8 +667,9 @@ class CapturedLookup:
             # after cache_populate() the eager module serves and trains the hot ids in cache_weight; the captured graphs
             # read and update the TT cores only -- the two would diverge silently
             raise RuntimeError("the row cache went live after capture(): captured lookups do not cover a live cache")
-        if float(m.learning_rate) != self._lr or float(m.eps) != self._eps:
-            raise RuntimeError("learning rate / eps are part of the captured backward: capture() again after changing them")
+        if float(m.learning_rate) != self._lr or float(m.eps) != self._eps or m._adam_key() != self._adam_key:
+            raise RuntimeError("learning rate / eps are part of the captured backward: capture() again after changing them "
+                               "(with OptimType.ADAM also betas, weight_decay and decoupled_weight_decay)")
         if self._pointers() != self._baked:
             raise RuntimeError("tt_cores / optimizer_state were re-allocated after capture() (.to(), .data = ..., "
                                "load_state_dict into new storage): capture() again")
@@ -669,8 +710,24 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  sparse: bool = True, use_cache: bool = False, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
-                 padding_idx: Optional[int] = None) -> None:
+                 padding_idx: Optional[int] = None, betas=(0.9, 0.999), weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False) -> None:
         super().__init__()
+        if optimizer == OptimType.ADAM:
+            if not (0.0 <= float(betas[0]) < 1.0 and 0.0 <= float(betas[1]) < 1.0):
+                raise ValueError(f"betas must lie in [0, 1), got {tuple(betas)}")
+            if float(weight_decay) < 0.0:
+                raise ValueError(f"weight_decay must not be negative, got {weight_decay}")
+            if use_cache and sparse:
+                raise ValueError(
+                    "use_cache=True with sparse=True and OptimType.ADAM is not supported: once cache_populate() makes the row "
+                    "cache live the cached rows are trained by a per-row optimiser of their own, and there is none for Adam "
+                    "(the reference has SGD and row-wise Adagrad only).  Use use_cache=False, or SGD / Adagrad with the cache.")
+        # OptimType.ADAM only (plain attributes, read at every step like learning_rate / eps)
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.weight_decay, self.decoupled_weight_decay = float(weight_decay), bool(decoupled_weight_decay)
+        self._adam_cache = None
+        self._adam_lean_cache = None
         if mode not in ("sum", "mean"):
             raise ValueError(f"mode must be 'sum' or 'mean', got {mode!r}")
         self.mode = mode
@@ -720,6 +777,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             self.tt_cores.append(nn.Parameter(torch.empty(shape, device=dev, dtype=torch.float32)))
             st_shape = shape if optimizer not in _SGD_LIKE else 0
             self.optimizer_state.append(torch.zeros(st_shape, device=dev, dtype=torch.float32))
+        if optimizer == OptimType.ADAM:
+            # optimizer_state{t} holds the first moment m; the second moment v and the device step words (one row of four
+            # int32 per table: word 0 = t, the steps applied; words 1-3 scratch of the kernels) are registered for ADAM only,
+            # so every other optimiser's state_dict keys are what they were
+            self.optimizer_state_v = BufferList("optimizer_state_v")
+            for c in self.tt_cores:
+                self.optimizer_state_v.append(torch.zeros_like(c.data))
+            self.register_buffer("adam_step", torch.zeros((num_tables, 4), device=dev, dtype=torch.int32))
         self.reset_parameters(weight_dist)
         self.use_cache = use_cache
         if use_cache:
@@ -834,6 +899,37 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         if sl is None or len(sl) != len(live) or any(b is not live.get(f"optimizer_state{t}") for t, b in enumerate(sl)):
             sl = self._state_list = tuple(self.optimizer_state)
         return sl
+
+    def _adam_key(self) -> Optional[tuple]:
+        if self.optimizer != OptimType.ADAM:
+            return None
+        return (float(self.learning_rate), float(self.eps), self.betas[0], self.betas[1], float(self.weight_decay),
+                bool(self.decoupled_weight_decay))
+
+    def _adam_params(self):
+        """``ttemb_adam_t`` of the current hyper-parameters (rebuilt when one of them changed)."""
+        key = self._adam_key()
+        c = self._adam_cache
+        if c is None or c[0] != key:
+            c = self._adam_cache = (key, _nat.make_adam(key[0], key[1], key[2:4], key[4], key[5]))
+        return c[1]
+
+    def _adam_lean(self):
+        """None, or (second moments, step words, hyper-parameters) of a one-table module for ``LeanCalls.backward``."""
+        if self.optimizer != OptimType.ADAM:
+            return None
+        c = self._adam_lean_cache   # (second moments, table 0's step words, the buffer they view): rebuilt when a buffer was replaced
+        live = self.optimizer_state_v._buffers
+        step = self._buffers["adam_step"]
+        if (c is None or c[2] is not step or len(c[0]) != len(live)
+                or any(b is not live.get(f"optimizer_state_v{t}") for t, b in enumerate(c[0]))):
+            c = self._adam_lean_cache = (tuple(self.optimizer_state_v), step[0], step)
+        return c[0], c[1], self._adam_params()
+
+    def adam_steps(self) -> List[int]:
+        """Steps applied so far, per table (reads the device words: synchronises)."""
+        assert self.optimizer == OptimType.ADAM
+        return [int(x) for x in self.adam_step[:, 0].tolist()]
 
     def _exact_requested(self) -> bool:
         if self.deterministic is not None:
@@ -1089,11 +1185,13 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  sparse: bool = True, use_cache: bool = True, cache_size: int = 0, hashtbl_size: int = 0,
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
-                 padding_idx: Optional[int] = None) -> None:
+                 padding_idx: Optional[int] = None, betas=(0.9, 0.999), weight_decay: float = 0.0,
+                 decoupled_weight_decay: bool = False) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
                          enforce_embedding_dim, batch_count, deterministic=deterministic, mode=mode,
-                         padding_idx=padding_idx)
+                         padding_idx=padding_idx, betas=betas, weight_decay=weight_decay,
+                         decoupled_weight_decay=decoupled_weight_decay)
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -668,14 +668,52 @@ struct Seg3 {
   long long n[TTEMB_MAX_CORES];
 };
 
+// Adam's part of the step kernel's arguments (v[0] == null: not Adam; st of the Seg3 is the first moment)
+struct AdamSeg {
+  float* v[TTEMB_MAX_CORES];
+  uint32_t* step;
+  float b1, omb1, b2, omb2, wd, grad_scale;
+  int32_t decoupled;
+};
+
+__global__ void adam_prepare_kernel(AdamPrep a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) adam_prepare(a);
+}
+
 // one launch for every core: blockIdx.y selects the core
 // `skip`: the poison word a grouped backward of this call left in the workspace header (FusedUpdate::poison_out), or null
-__global__ void fused_step_kernel(Seg3 seg, float lr, float eps, int adagrad, const uint32_t* __restrict__ skip) {
+__global__ void fused_step_kernel(Seg3 seg, float lr, float eps, int adagrad, const uint32_t* __restrict__ skip, AdamSeg ad) {
   if (skip != nullptr && *skip != 0u) return;   // the gradients are NaN and the host hears of it: parameters stay as they are
   const int t = blockIdx.y;
   float* __restrict__ w = seg.w[t];
   const float* __restrict__ g = seg.g[t];
   const long long n = seg.n[t];
+  if (ad.v[0] != nullptr) {   // Adam / AdamW on the pending step words (adam_prepare_kernel ran before); the first thread commits t
+    AdamCoef ac;
+    ac.step_size = lr * __uint_as_float(ad.step[2]);
+    ac.inv_sqrt_bc2 = __uint_as_float(ad.step[3]);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ad.step[0] = ad.step[1];
+    float* __restrict__ m = seg.st[t];
+    float* __restrict__ v = ad.v[t];
+    const float gs = ad.grad_scale;
+    for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * blockDim.x * 4) {
+      if (i + 3 < n) {
+        float4 wv = *reinterpret_cast<float4*>(w + i), mv = *reinterpret_cast<float4*>(m + i), vv = *reinterpret_cast<float4*>(v + i);
+        const float4 gv = *reinterpret_cast<const float4*>(g + i);
+        adam_element(wv.x, mv.x, vv.x, gv.x * gs, ac, lr, eps, ad.b1, ad.omb1, ad.b2, ad.omb2, ad.wd, ad.decoupled);
+        adam_element(wv.y, mv.y, vv.y, gv.y * gs, ac, lr, eps, ad.b1, ad.omb1, ad.b2, ad.omb2, ad.wd, ad.decoupled);
+        adam_element(wv.z, mv.z, vv.z, gv.z * gs, ac, lr, eps, ad.b1, ad.omb1, ad.b2, ad.omb2, ad.wd, ad.decoupled);
+        adam_element(wv.w, mv.w, vv.w, gv.w * gs, ac, lr, eps, ad.b1, ad.omb1, ad.b2, ad.omb2, ad.wd, ad.decoupled);
+        *reinterpret_cast<float4*>(m + i) = mv;
+        *reinterpret_cast<float4*>(v + i) = vv;
+        *reinterpret_cast<float4*>(w + i) = wv;
+      } else {
+        for (long long j = i; j < n; ++j)
+          adam_element(w[j], m[j], v[j], g[j] * gs, ac, lr, eps, ad.b1, ad.omb1, ad.b2, ad.omb2, ad.wd, ad.decoupled);
+      }
+    }
+    return;
+  }
   for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n;
        i += (long long)gridDim.x * blockDim.x * 4) {
     if (i + 3 < n) {
@@ -721,6 +759,62 @@ static int run_adagrad(float* w, float* state, const float* g, int64_t n, float 
   const int64_t blocks = (n + threads - 1) / threads;
   hipLaunchKernelGGL(adagrad_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, state, g, n, lr, eps);
   return check_hip(hipGetLastError(), "adagrad_step_kernel");
+}
+
+int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd) {
+  if (hp == nullptr || step == nullptr) return fail(TTEMB_E_BADARG, "adam: null hyper-parameters / step words");
+  if (!(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0))
+    return fail(TTEMB_E_BADARG, "adam: betas (%g, %g) outside [0, 1)", hp->beta1, hp->beta2);
+  if (!(hp->lr >= 0.f) || !(hp->eps >= 0.f) || !(hp->weight_decay >= 0.f))
+    return fail(TTEMB_E_BADARG, "adam: negative lr / eps / weight_decay");
+  if (reinterpret_cast<uintptr_t>(step) & 15) return fail(TTEMB_E_BADARG, "adam: the step words must be 16-byte aligned");
+  upd->lr = hp->lr;
+  upd->eps = hp->eps;
+  upd->step = reinterpret_cast<uint32_t*>(step);
+  upd->b1 = (float)hp->beta1;
+  upd->omb1 = (float)(1.0 - hp->beta1);
+  upd->b2 = (float)hp->beta2;
+  upd->omb2 = (float)(1.0 - hp->beta2);
+  upd->wd = hp->weight_decay;
+  upd->decoupled = hp->decoupled != 0 ? 1 : 0;
+  upd->beta1 = hp->beta1;
+  upd->beta2 = hp->beta2;
+  return TTEMB_OK;
+}
+
+int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
+                    hipStream_t st) {
+  Seg3 seg;
+  AdamSeg ad;
+  memset(&seg, 0, sizeof(seg));
+  memset(&ad, 0, sizeof(ad));
+  long long nmax = 0;
+  for (int t = 0; t < T; ++t) {
+    if (n[t] > 0 && (upd.w[t] == nullptr || upd.st[t] == nullptr || upd.v[t] == nullptr || g[t] == nullptr))
+      return fail(TTEMB_E_BADARG, "adam: null buffer");
+    if ((reinterpret_cast<uintptr_t>(upd.w[t]) | reinterpret_cast<uintptr_t>(upd.st[t]) | reinterpret_cast<uintptr_t>(upd.v[t]) |
+         reinterpret_cast<uintptr_t>(g[t])) & 15)
+      return fail(TTEMB_E_BADARG, "adam: weights, moments and gradients must be 16-byte aligned");
+    seg.w[t] = upd.w[t];
+    seg.st[t] = upd.st[t];
+    seg.g[t] = g[t];
+    seg.n[t] = n[t];
+    ad.v[t] = upd.v[t];
+    nmax = n[t] > nmax ? n[t] : nmax;
+  }
+  if (nmax == 0 || ad.v[0] == nullptr) return TTEMB_OK;
+  ad.step = upd.step;
+  ad.b1 = upd.b1; ad.omb1 = upd.omb1; ad.b2 = upd.b2; ad.omb2 = upd.omb2;
+  ad.wd = upd.wd;
+  ad.grad_scale = grad_scale;
+  ad.decoupled = upd.decoupled;
+  hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, st, adam_prep_of(upd));
+  int rc = check_hip(hipGetLastError(), "adam_prepare_kernel");
+  if (rc) return rc;
+  long long blocks = (nmax / 4 + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)T), dim3(256), 0, st, seg, upd.lr, upd.eps, 0, skip, ad);
+  return check_hip(hipGetLastError(), "fused_step_kernel (adam)");
 }
 
 static int check_lookup_args(const void* cores, const void* indices, int64_t nnz, int64_t B) {
@@ -1067,12 +1161,13 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
                           const int64_t* indices, const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
                           const int32_t* nnz_dev, int64_t B, const float* d_output, float lr, float eps,
                           void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
-                          void* stream) {
+                          void* stream, const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr) {
   Entry e;
   int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
   const DevShape& ds = e.ds;
-  if (nnz == 0) return TTEMB_OK;  // zero gradient: SGD is a no-op, Adagrad adds 0 and divides 0
+  // zero gradient: SGD is a no-op, Adagrad adds 0 and divides 0; an Adam call without ids is defined as a no-op too (t stays)
+  if (nnz == 0) return TTEMB_OK;
   if (d_output == nullptr) return fail(TTEMB_E_BADARG, "d_output is null");
   const int64_t need = kFast3HeaderBytes + grad_scratch_bytes(ds);
   if (workspace == nullptr || workspace_bytes < need)
@@ -1093,17 +1188,32 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   bool aligned4 = true;
   FusedUpdate upd;
   memset(&upd, 0, sizeof(upd));
+  if (adam != nullptr) upd = *adam;   // (lr, eps, the step words and the Adam hyper-parameters: adam_fill)
   for (int t = 0; t < ds.T; ++t) {
     upd.w[t] = cores[t];
     upd.st[t] = opt_state ? opt_state[t] : nullptr;
-    aligned4 = aligned4 && cores[t] != nullptr && (!opt_state || opt_state[t] != nullptr);
+    upd.v[t] = adam != nullptr ? exp_avg_sq[t] : nullptr;
+    aligned4 = aligned4 && cores[t] != nullptr && (!opt_state || opt_state[t] != nullptr) && (adam == nullptr || exp_avg_sq[t] != nullptr);
   }
   if (!aligned4) return fail(TTEMB_E_BADARG, "null core / optimizer state");
-  upd.lr = lr;
-  upd.eps = eps;
+  if (adam == nullptr) {
+    upd.lr = lr;
+    upd.eps = eps;
+  }
   rc = backward_into(r, ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, gp, rest_ws, rest, plan, plan_bytes, e.st,
                      e.header, fused ? &upd : nullptr);
   if (rc || fused) return rc;
+  const uint32_t* header_skip =
+      r.grouped ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(e.header) + kHeaderPoisonOffset) : nullptr;
+  if (adam != nullptr) {   // the Adam step of every core from the gradient scratch: a prepare launch and the step launch
+    const float* g[TTEMB_MAX_CORES];
+    long long n[TTEMB_MAX_CORES];
+    for (int t = 0; t < ds.T; ++t) {
+      g[t] = gp.c[t];
+      n[t] = (long long)ds.p[t] * ds.row_len[t];
+    }
+    return run_adam_arrays(upd, g, n, ds.T, 1.f, header_skip, e.st);
+  }
   Seg3 seg;
   memset(&seg, 0, sizeof(seg));
   int64_t nmax = 0;
@@ -1120,10 +1230,25 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   int64_t blocks = (nmax / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
   // (a grouped backward left its verdict in the header's poison word: a poisoned plan leaves the parameters alone)
+  AdamSeg no_adam;
+  memset(&no_adam, 0, sizeof(no_adam));
   hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, e.st, seg, lr, eps,
-                     opt_state ? 1 : 0,
-                     r.grouped ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(e.header) + kHeaderPoisonOffset) : nullptr);
+                     opt_state ? 1 : 0, header_skip, no_adam);
   return check_hip(hipGetLastError(), "fused_step_kernel");
+}
+
+int ttemb_backward_adam(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                        int32_t* step, const int64_t* indices, const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
+                        const int32_t* nnz_dev, int64_t B, const float* d_output, const ttemb_adam_t* hp,
+                        void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream) {
+  ApiRange api_range("ttemb_backward_adam");
+  if (exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exp_avg / exp_avg_sq is null");
+  FusedUpdate adam;
+  memset(&adam, 0, sizeof(adam));
+  int rc = adam_fill(hp, step, &adam);
+  if (rc) return rc;
+  return fused_backward(shape, cores, exp_avg, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, hp->lr, hp->eps, workspace,
+                        workspace_bytes, plan, plan_bytes, stream, &adam, exp_avg_sq);
 }
 
 int ttemb_backward_sgd(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices,
@@ -1187,7 +1312,8 @@ int ttemb_forward_window(const ttemb_shape_t* shape, const float* const* cores, 
 
 static int backward_window(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, float* const* d_cores,
                            const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B,
-                           const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream) {
+                           const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream,
+                           const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr) {
   Entry e;
   int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
@@ -1205,13 +1331,18 @@ static int backward_window(const ttemb_shape_t* shape, float* const* cores, floa
   FusedUpdate upd;
   memset(&upd, 0, sizeof(upd));
   if (d_cores == nullptr) {
+    if (adam != nullptr) upd = *adam;   // (lr, eps, the step words and the Adam hyper-parameters: adam_fill)
     for (int t = 0; t < ds.T; ++t) {
       upd.w[t] = cores[t];
       upd.st[t] = opt_state ? opt_state[t] : nullptr;
-      if (cores[t] == nullptr || (opt_state && opt_state[t] == nullptr)) return fail(TTEMB_E_BADARG, "null core / optimizer state");
+      upd.v[t] = adam != nullptr ? exp_avg_sq[t] : nullptr;
+      if (cores[t] == nullptr || (opt_state && opt_state[t] == nullptr) || (adam != nullptr && exp_avg_sq[t] == nullptr))
+        return fail(TTEMB_E_BADARG, "null core / optimizer state");
     }
-    upd.lr = lr;
-    upd.eps = eps;
+    if (adam == nullptr) {
+      upd.lr = lr;
+      upd.eps = eps;
+    }
   }
   return launch_backward_window_fast3(ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, d_output, dp, e.ws, e.ws_bytes, e.st,
                                       d_cores == nullptr ? &upd : nullptr, e.header);
@@ -1241,6 +1372,36 @@ int ttemb_backward_adagrad_window(const ttemb_shape_t* shape, float* const* core
   if (opt_state == nullptr) return fail(TTEMB_E_BADARG, "opt_state is null");
   return backward_window(shape, cores, opt_state, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, lr, eps, workspace,
                          workspace_bytes, stream);
+}
+
+int ttemb_backward_adam_window(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                               int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total,
+                               int64_t bag0, int64_t B, const float* d_output, const ttemb_adam_t* hp, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  ApiRange api_range("ttemb_backward_adam_window");
+  if (exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exp_avg / exp_avg_sq is null");
+  FusedUpdate adam;
+  memset(&adam, 0, sizeof(adam));
+  int rc = adam_fill(hp, step, &adam);
+  if (rc) return rc;
+  return backward_window(shape, cores, exp_avg, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, hp->lr, hp->eps, workspace,
+                         workspace_bytes, stream, &adam, exp_avg_sq);
+}
+
+int ttemb_adam_step(float* weights, float* exp_avg, float* exp_avg_sq, int32_t* step, const float* grads, int64_t n,
+                    float grad_scale, const ttemb_adam_t* hp, const float* skip, void* stream) {
+  ApiRange api_range("ttemb_adam_step");
+  if (n < 0) return fail(TTEMB_E_BADARG, "negative n");
+  FusedUpdate upd;
+  memset(&upd, 0, sizeof(upd));
+  int rc = adam_fill(hp, step, &upd);
+  if (rc || n == 0) return rc;
+  upd.w[0] = weights;
+  upd.st[0] = exp_avg;
+  upd.v[0] = exp_avg_sq;
+  if (weights == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || grads == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
+  const long long nn = n;
+  return run_adam_arrays(upd, &grads, &nn, 1, grad_scale, reinterpret_cast<const uint32_t*>(skip), reinterpret_cast<hipStream_t>(stream));
 }
 
 int ttemb_sgd_step(float* weights, const float* grads, int64_t n, float lr, void* stream) {

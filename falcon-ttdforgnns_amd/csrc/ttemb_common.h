@@ -94,11 +94,18 @@ int launch_forward_fast3(const DevShape& s, const CorePtrs& cores, const int64_t
 // `header`: kFast3HeaderBytes at the start of the caller's workspace, the same address for every op on that workspace: the
 // words of the grouping pass that outlive a call (its epoch, the pre-tagged range counters).  Any content is valid.
 constexpr int64_t kFast3HeaderBytes = 40960;
-// optimiser step folded into the last backward kernel (w == nullptr: none, gradients are written instead)
-struct FusedUpdate {
+// optimiser step folded into the last backward kernel (w == nullptr: none, gradients are written instead): the part the
+// kernels take by value (FusedUpdate below adds what only the host reads)
+struct FusedUpdateK {
   float* w[TTEMB_MAX_CORES];
-  float* st[TTEMB_MAX_CORES];   // Adagrad state, or null for SGD
+  float* st[TTEMB_MAX_CORES];   // Adagrad state / Adam's first moment, or null for SGD
   float lr, eps;
+  // Adam (v[0] != null; st = the first moment m, v = the second): the step words (see AdamPrep) and the hyper-parameters
+  float* v[TTEMB_MAX_CORES];
+  uint32_t* step;
+  float b1, omb1, b2, omb2;     // beta, 1 - beta (each rounded once from the double)
+  float wd;                     // weight decay; decoupled != 0: w -= lr wd w (AdamW), else g += wd w (Adam)
+  int32_t decoupled;
   // A word of the workspace header the finalize kernel sets to 1 when the plan it ran on is POISONED and the host hears of
   // it (fault word present), else to 0 (sticky = 1: a later piece of the same call only ever sets it): the optimiser step
   // that follows a gradient-writing route (padded ranks, merged pairs, calls in pieces) reads it and leaves the parameters
@@ -106,6 +113,60 @@ struct FusedUpdate {
   uint32_t* poison_out;
   int32_t sticky;
 };
+// ... and the host's view of it: + the betas in double, which only the launch that carries an AdamPrep needs (adam_prep_of)
+struct FusedUpdate : FusedUpdateK {
+  double beta1, beta2;
+};
+// Adam's step count lives on the device, in four 32-bit words the caller owns: [0] t, the steps applied so far; [1] t + 1,
+// [2] 1 / (1 - b1^(t+1)) and [3] 1 / sqrt(1 - b2^(t+1)) as float bits -- the PENDING step.  One lane of a kernel that runs
+// before the stepping kernel of the same call forms words 1-3 from word 0 (adam_prepare); every workgroup of the stepping
+// kernel reads words 2-3 only, and its first thread commits word 0 = word 1 unless the step is skipped.  No workgroup reads
+// a word that another workgroup of the same launch writes, so t advances exactly once per applied step, and a skipped step
+// (w, m, v and t as they were) can be repeated.
+struct AdamPrep {
+  uint32_t* step;   // null: not an Adam call
+  double b1, b2;
+};
+__device__ __forceinline__ void adam_prepare(const AdamPrep& a) {
+  const uint32_t t = a.step[0] + 1u;
+  double p1 = 1.0, p2 = 1.0, x1 = a.b1, x2 = a.b2;   // beta^t by squaring, in double (1 - b2^t is ~1e-3 t: fp32 would lose four digits)
+  for (uint32_t n = t; n != 0u; n >>= 1) {
+    if (n & 1u) { p1 *= x1; p2 *= x2; }
+    x1 *= x1; x2 *= x2;
+  }
+  a.step[1] = t;
+  a.step[2] = __float_as_uint((float)(1.0 / (1.0 - p1)));
+  a.step[3] = __float_as_uint((float)(1.0 / sqrt(1.0 - p2)));
+}
+// what the stepping kernel holds per workgroup: lr / (1 - b1^t) and 1 / sqrt(1 - b2^t)
+struct AdamCoef {
+  float step_size, inv_sqrt_bc2;
+};
+// One element of the Adam / AdamW step (torch.optim.Adam / AdamW without amsgrad).  A zero denominator (v = 0 and eps = 0: an
+// element that has never seen a gradient) leaves w alone instead of dividing 0 by 0.
+__device__ __forceinline__ void adam_element(float& w, float& m, float& v, float g, const AdamCoef& c, float lr, float eps, float b1,
+                                             float omb1, float b2, float omb2, float wd, int decoupled) {
+  if (decoupled) w -= lr * wd * w; else g += wd * w;
+  m = b1 * m + omb1 * g;
+  v = b2 * v + omb2 * (g * g);
+  const float denom = sqrtf(v) * c.inv_sqrt_bc2 + eps;
+  if (denom > 0.f) w -= c.step_size * m / denom;
+}
+inline AdamPrep adam_prep_of(const FusedUpdate& u) {
+  AdamPrep a;
+  a.step = u.v[0] != nullptr ? u.step : nullptr;
+  a.b1 = u.beta1;
+  a.b2 = u.beta2;
+  return a;
+}
+// a ttemb_adam_t into the lr, eps and Adam fields of a FusedUpdate (ttemb_api.hip); TTEMB_E_BADARG outside torch.optim.Adam's domain
+int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd);
+// The Adam step of `T` arrays (upd.w / st / v [t], gradients g[t] * grad_scale, n[t] floats, all 16-byte aligned) from gradients
+// in memory: a one-lane launch that forms the pending step words, then one stepping launch (ttemb_api.hip).  skip: null, or a
+// device word that, non-zero, leaves everything as it was
+int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
+                    hipStream_t st);
+
 // where that word sits in the header: behind the epoch words and the banks of range counters (16 + 8 * 512 * 8 bytes)
 constexpr int64_t kHeaderPoisonOffset = 16 + 8 * 512 * 8;
 static_assert(kHeaderPoisonOffset + 8 <= kFast3HeaderBytes, "the poison word lies inside the header");

@@ -879,4 +879,41 @@ int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores
                      workspace_bytes, stream);
 }
 
+int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                              int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
+                              const float* d_output, const ttemb_adam_t* hp, void* workspace, int64_t workspace_bytes,
+                              const void* plan, int64_t plan_bytes, void* stream) {
+  (void)plan;
+  (void)plan_bytes;
+  ExShape s;
+  int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
+  if (rc) return rc;
+  FusedUpdate upd;
+  memset(&upd, 0, sizeof(upd));
+  if ((rc = adam_fill(hp, step, &upd))) return rc;
+  if (cores == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exact mode: null cores / moments");
+  if (nnz == 0) return TTEMB_OK;   // a call without ids is a no-op (t stays)
+  // the dense exact gradient into scratch behind the exact workspace, then the elementwise step (it has no order)
+  const int64_t base = (ex_layout(s, nnz).total + 255) / 256 * 256;
+  float* grads[TTEMB_MAX_CORES] = {nullptr, nullptr, nullptr, nullptr};
+  const float* g[TTEMB_MAX_CORES];
+  long long n[TTEMB_MAX_CORES];
+  int64_t off = base;
+  for (int t = 0; t < shape->T; ++t) {
+    n[t] = (long long)shape->p[t] * shape->R[t] * shape->q[t] * shape->R[t + 1];
+    grads[t] = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + off);
+    g[t] = grads[t];
+    off += (n[t] * 4 + 255) / 256 * 256;
+    upd.w[t] = cores[t];
+    upd.st[t] = exp_avg[t];
+    upd.v[t] = exp_avg_sq[t];
+  }
+  if (workspace == nullptr || workspace_bytes < off)
+    return fail(TTEMB_E_WORKSPACE, "exact Adam: workspace of %lld bytes, need %lld (the exact workspace and the gradient scratch)",
+                (long long)workspace_bytes, (long long)off);
+  rc = ex_backward(kExDense, shape, cores, nullptr, indices, offsets, nnz, B, d_output, grads, 0.0f, 0.0f, workspace, base, stream);
+  if (rc) return rc;
+  return run_adam_arrays(upd, g, n, shape->T, 1.f, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

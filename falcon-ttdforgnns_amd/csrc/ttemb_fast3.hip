@@ -2434,7 +2434,9 @@ constexpr int kReduceU = TTEMB_REDUCE_U;      // row loads in flight per bucket 
 // with float atomics, a whole row (contiguous floats) per non-empty bucket, instead of a slab per tile (a 4-core
 // table with a merged last pair has 0.9 MB slabs: 256 of them were 236 MB to write and read back).
 template <int ROW2, int kRowsMax, int NWB, bool SHARED>
-__global__ __launch_bounds__(NWB * 64) void fast3_dg2_reduce_kernel(GroupPlan plan, int G, uint32_t p2, uint32_t kRowsB, uint32_t stride) {
+__global__ __launch_bounds__(NWB * 64) void fast3_dg2_reduce_kernel(GroupPlan plan, int G, uint32_t p2, uint32_t kRowsB, uint32_t stride,
+                                                                     AdamPrep adam) {
+  if (adam.step != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) adam_prepare(adam);   // (for the finalize kernel)
   extern __shared__ uint32_t lds_u[];   // [p2 + 1] bucket starts | [p2] cursors | [kRowsMax] row list (uint16)
   uint32_t* bstart = lds_u;
   uint32_t* cursor = lds_u + p2 + 1;
@@ -2796,9 +2798,11 @@ __device__ __forceinline__ void epilogue_unit(
 
 template <int Q0, int Q1, int Q2, int R1, int R2>
 __global__ __launch_bounds__((EpiCfg<Q0, Q1, Q2, R1, R2>::WAVES * 64)) void fast3_group_epilogue_kernel(
-    const float* __restrict__ G0, const float* __restrict__ G1, uint32_t p0, uint32_t p1, uint32_t gpw, uint32_t slices, GroupPlan plan) {
+    const float* __restrict__ G0, const float* __restrict__ G1, uint32_t p0, uint32_t p1, uint32_t gpw, uint32_t slices, GroupPlan plan,
+    AdamPrep adam) {
   using C = Cfg<Q0, Q1, Q2, R1, R2>;
   constexpr int EW = EpiCfg<Q0, Q1, Q2, R1, R2>::WAVES;
+  if (adam.step != nullptr && blockIdx.x == 0 && threadIdx.x == 0) adam_prepare(adam);   // (the finalize kernel steps with these words)
   __shared__ __attribute__((aligned(16))) float dpbuf_all[EW][16 * (C::N1 + 4)];
   __shared__ __attribute__((aligned(16))) float g1buf[R1 * C::LDG];
   const uint32_t wave = threadIdx.x >> 6;
@@ -2817,11 +2821,17 @@ __global__ __launch_bounds__((EpiCfg<Q0, Q1, Q2, R1, R2>::WAVES * 64)) void fast
 // non-empty groups; dG1 = sum of the per-slice slabs.  A workgroup owns 32 consecutive outputs; its 8 lane
 // rows split the terms, so every load instruction reads 128 contiguous bytes per row and many
 // are in flight; the 8 partial sums meet in LDS.  Every output is written exactly once.
-__device__ __forceinline__ void finalize_emit(const FusedUpdate& upd, int t, float* __restrict__ grad, int idx, float g) {
+__device__ __forceinline__ void finalize_emit(const FusedUpdateK& upd, const AdamCoef& ac, int t, float* __restrict__ grad, int idx, float g) {
   if (upd.w[0] == nullptr) {   // dense mode: the gradient itself (eps = 1: added to what an earlier piece of the call left)
     grad[idx] = upd.eps != 0.f ? grad[idx] + g : g;
   } else if (upd.st[0] == nullptr) {   // fused SGD (tt_embeddings_cuda.cu:381-397), every row
     upd.w[t][idx] -= upd.lr * g;
+  } else if (upd.v[0] != nullptr) {    // fused Adam / AdamW (include/ttemb.h "Fused Adam / AdamW"), every row
+    float w = upd.w[t][idx], m = upd.st[t][idx], v = upd.v[t][idx];
+    adam_element(w, m, v, g, ac, upd.lr, upd.eps, upd.b1, upd.omb1, upd.b2, upd.omb2, upd.wd, upd.decoupled);
+    upd.st[t][idx] = m;
+    upd.v[t][idx] = v;
+    upd.w[t][idx] = w;
   } else {                             // fused Adagrad (tt_embeddings_cuda.cu:399-419)
     const float s2 = upd.st[t][idx] + g * g;
     upd.st[t][idx] = s2;
@@ -2832,7 +2842,7 @@ __device__ __forceinline__ void finalize_emit(const FusedUpdate& upd, int t, flo
 __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int tiles, int slices, int p0, int p1,
                                                              int g2_floats, int row0, int g1_floats, int q2, int r2,
                                                              float* __restrict__ dG0, float* __restrict__ dG1,
-                                                             float* __restrict__ dG2, FusedUpdate upd, int all_parts) {
+                                                             float* __restrict__ dG2, FusedUpdateK upd, int all_parts) {
   __shared__ float part[8][33];
   const int x = threadIdx.x & 31, y = threadIdx.x >> 5;
   const int n0 = p0 * row0;
@@ -2847,6 +2857,14 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
   const bool loud = poisoned && plan.fault_host != nullptr;
   if (upd.poison_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0 && (loud || !upd.sticky)) *upd.poison_out = loud ? 1u : 0u;
   if (loud && upd.w[0] != nullptr) return;   // (wave- and grid-uniform)
+  // Adam: the pending step's bias corrections, formed by one lane of an earlier kernel of this backward (AdamPrep); this launch
+  // reads words 2-3 and its first thread commits t.  A skipped step (the return above) leaves t with w, m and v.
+  AdamCoef ac = {0.f, 0.f};
+  if (upd.v[0] != nullptr) {
+    ac.step_size = upd.lr * __uint_as_float(upd.step[2]);
+    ac.inv_sqrt_bc2 = __uint_as_float(upd.step[3]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) upd.step[0] = upd.step[1];
+  }
   const float poison = poisoned ? __uint_as_float(0x7fc00000u) : 0.f;
   const bool sparse = all_parts ? true : sparse_any;          // dG0 parts: skip the groups without ids by their counts
   const bool sparse_g1 = all_parts ? false : sparse_any;      // dG1 slabs: skip the slices without ids by their flags
@@ -2901,10 +2919,10 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
     __syncthreads();
     if (threadIdx.x < 8 && o < n0) {
       const float4 a = part4[0][xb], b = part4[1][xb], c4 = part4[2][xb], d4 = part4[3][xb];
-      finalize_emit(upd, 0, dG0, o + 0, (a.x + b.x) + (c4.x + d4.x) + poison);
-      finalize_emit(upd, 0, dG0, o + 1, (a.y + b.y) + (c4.y + d4.y) + poison);
-      finalize_emit(upd, 0, dG0, o + 2, (a.z + b.z) + (c4.z + d4.z) + poison);
-      finalize_emit(upd, 0, dG0, o + 3, (a.w + b.w) + (c4.w + d4.w) + poison);
+      finalize_emit(upd, ac, 0, dG0, o + 0, (a.x + b.x) + (c4.x + d4.x) + poison);
+      finalize_emit(upd, ac, 0, dG0, o + 1, (a.y + b.y) + (c4.y + d4.y) + poison);
+      finalize_emit(upd, ac, 0, dG0, o + 2, (a.z + b.z) + (c4.z + d4.z) + poison);
+      finalize_emit(upd, ac, 0, dG0, o + 3, (a.w + b.w) + (c4.w + d4.w) + poison);
     }
     return;
   }
@@ -2929,10 +2947,10 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
       tot.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
       tot.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
     }
-    finalize_emit(upd, 1, dG1, o + 0, tot.x + poison);
-    finalize_emit(upd, 1, dG1, o + 1, tot.y + poison);
-    finalize_emit(upd, 1, dG1, o + 2, tot.z + poison);
-    finalize_emit(upd, 1, dG1, o + 3, tot.w + poison);
+    finalize_emit(upd, ac, 1, dG1, o + 0, tot.x + poison);
+    finalize_emit(upd, ac, 1, dG1, o + 1, tot.y + poison);
+    finalize_emit(upd, ac, 1, dG1, o + 2, tot.z + poison);
+    finalize_emit(upd, ac, 1, dG1, o + 3, tot.w + poison);
     return;
   }
   // (dG2 outputs come first, 32 per workgroup; dG0's workgroups start at a 32-aligned output of their own)
@@ -2983,9 +3001,9 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
       const int row2 = q2 * r2;
       const int i2 = e / row2, w = e - i2 * row2;
       const int kk = w / r2, c2 = w - kk * r2;
-      finalize_emit(upd, 2, dG2, i2 * row2 + c2 * q2 + kk, tot);
+      finalize_emit(upd, ac, 2, dG2, i2 * row2 + c2 * q2 + kk, tot);
     } else if (e < g2_floats + n0) {
-      finalize_emit(upd, 0, dG0, e - g2_floats, tot);
+      finalize_emit(upd, ac, 0, dG0, e - g2_floats, tot);
     }
   }
 }
@@ -3511,9 +3529,9 @@ static int run_wide_gemm(WideGemm g, const DevShape& s, const GroupPlan& plan, h
   return check_hip(hipGetLastError(), what);
 }
 
-static int run_wide_rows(const DevShape& s, const GroupPlan& plan, hipStream_t st) {
+static int run_wide_rows(const DevShape& s, const GroupPlan& plan, hipStream_t st, const AdamPrep& adam = AdamPrep{nullptr, 0.0, 0.0}) {
   hipLaunchKernelGGL(wide3_rows_kernel, dim3((unsigned)s.p[1]), dim3(256), 0, st, plan, (uint32_t)s.p[0], (uint32_t)s.q[0],
-                     (uint32_t)wide_rows_stride(s), plan.wrows, plan.wnrows);
+                     (uint32_t)wide_rows_stride(s), plan.wrows, plan.wnrows, adam);
   return check_hip(hipGetLastError(), "wide3_rows_kernel");
 }
 
@@ -3682,8 +3700,10 @@ static int run_backward_wide(const DevShape& s, const CorePtrs& cores, const Gro
   using C = WideCfg<Q0, Q1, Q2, R1, R2>;
   const int64_t G = num_groups(s);
   profile_begin(1, st);
-  int rc = run_wide_rows(s, plan, st);   // (the workspace of this call; the forward's lists are not part of the plan)
+  // (the workspace of this call; the forward's lists are not part of the plan.  Adam: its one lane forms the pending step words)
+  int rc = run_wide_rows(s, plan, st, adam_prep_of(upd));
   if (rc) return rc;
+  const AdamPrep no_adam{nullptr, 0.0, 0.0};
   static_assert(C::ROW2 % 256 == 0, "the E reduce takes 256 columns per launch row");
   const int tiles = (int)reduce_tiles(nnz);
   const size_t reduce_lds = (size_t)(2 * s.p[2] + 1) * 4 + kRowsB * 2;
@@ -3725,13 +3745,13 @@ static int run_backward_wide(const DevShape& s, const CorePtrs& cores, const Gro
     rc = launch_zero(plan.g2part, (size_t)s.p[2] * C::ROW2 * 4, st, "zero the shared dG2 slab");
     if (rc) return rc;
     hipLaunchKernelGGL((fast3_dg2_reduce_kernel<256, kRowsB, NWB, true>), dim3((unsigned)tiles, C::ROW2 / 256), dim3(NWB * 64), reduce_lds,
-                       st, plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2);
+                       st, plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2, no_adam);
   } else {
 #if defined(TTEMB_ABL) && (TTEMB_ABL & 2048)
     if (nnz < 0)
 #endif
     hipLaunchKernelGGL((fast3_dg2_reduce_kernel<256, kRowsB, NWB, false>), dim3((unsigned)tiles, C::ROW2 / 256), dim3(NWB * 64), reduce_lds,
-                       st, plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2);
+                       st, plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2, no_adam);
   }
   rc = check_hip(hipGetLastError(), "fast3_dg2_reduce_kernel (wide)");
   if (rc) return rc;
@@ -3891,17 +3911,21 @@ static int run_backward(const DevShape& s, const CorePtrs& cores, const GroupPla
   }
   const int tiles = (int)reduce_tiles(nnz);
   const size_t reduce_lds = (size_t)(2 * s.p[2] + 1) * 4 + kRowsB * 2;
+  // Adam's pending step words are formed by one lane of the launch before the finalize kernel: the epilogue kernel, or, where the
+  // chunk kernel formed the group products (no epilogue launch; never with the fused dG2 form), the dG2 reduction
+  const AdamPrep no_adam{nullptr, 0.0, 0.0};
+  const AdamPrep reduce_adam = gfuse ? adam_prep_of(upd) : no_adam, epi_adam = gfuse ? no_adam : adam_prep_of(upd);
   if (fused) {
     // nothing: the slabs are written
   } else if (shared_slab(s)) {
     rc = launch_zero(plan.g2part, (size_t)s.p[2] * C::ROW2 * 4, st, "zero the shared dG2 slab");
     if (rc) return rc;
     hipLaunchKernelGGL((fast3_dg2_reduce_kernel<C::ROW2, kRowsB, NWB, true>), dim3((unsigned)tiles), dim3(NWB * 64), reduce_lds, st,
-                       plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2);
+                       plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2, reduce_adam);
 
   } else {
     hipLaunchKernelGGL((fast3_dg2_reduce_kernel<C::ROW2, kRowsB, NWB, false>), dim3((unsigned)tiles), dim3(NWB * 64), reduce_lds, st,
-                       plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2);
+                       plan, (int)G, (uint32_t)s.p[2], (uint32_t)reduce_rows(nnz), (uint32_t)C::ROW2, reduce_adam);
   }
   rc = check_hip(hipGetLastError(), "fast3_dg2_reduce_kernel");
   if (rc) return rc;
@@ -3914,7 +3938,8 @@ static int run_backward(const DevShape& s, const CorePtrs& cores, const GroupPla
     if (fused)
 #endif
     hipLaunchKernelGGL((fast3_group_epilogue_kernel<Q0, Q1, Q2, R1, R2>), dim3(epi_blocks),
-                       dim3(EW * 64), 0, st, cores.c[0], cores.c[1], (uint32_t)s.p[0], (uint32_t)s.p[1], (uint32_t)gpw, (uint32_t)slices, plan);
+                       dim3(EW * 64), 0, st, cores.c[0], cores.c[1], (uint32_t)s.p[0], (uint32_t)s.p[1], (uint32_t)gpw, (uint32_t)slices, plan,
+                       epi_adam);
     profile_end(8, st);
     rc = check_hip(hipGetLastError(), "fast3_group_epilogue_kernel");
     if (rc) return rc;

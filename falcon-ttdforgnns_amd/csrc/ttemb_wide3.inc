@@ -129,8 +129,9 @@ struct WideGemm {
 // compacted K of the dG1 GEMM.  A frontier with locality (METIS-ordered ids, small batches) touches a fraction of the
 // p0 p1 groups; the GEMMs then do that fraction of the work.  One workgroup per i1.
 __global__ __launch_bounds__(256) void wide3_rows_kernel(GroupPlan plan, uint32_t p0, uint32_t q0, uint32_t stride, uint32_t* __restrict__ rows,
-                                                         uint32_t* __restrict__ n_rows) {
+                                                         uint32_t* __restrict__ n_rows, AdamPrep adam) {
   __shared__ uint32_t wave_sums[4];
+  if (adam.step != nullptr && blockIdx.x == 0 && threadIdx.x == 0) adam_prepare(adam);   // (a backward's: for its finalize kernel)
   const uint32_t i1 = blockIdx.x;
   uint32_t base = 0;
   for (uint32_t i0_0 = 0; i0_0 < p0; i0_0 += 256u) {

@@ -107,6 +107,29 @@ def tt_adagrad_backward(batch_count: int, D: int, learning_rate: float, eps: flo
                                   float(learning_rate), float(eps), _ws(d_output.device))
 
 
+def tt_adam_backward(batch_count: int, D: int, learning_rate: float, eps: float, beta1: float, beta2: float,
+                     weight_decay: float, decoupled_weight_decay: bool, tt_p_shapes, tt_q_shapes, tt_ranks, L, nnz: int,
+                     indices, rowidx, tableidx, d_output: torch.Tensor, exp_avg, exp_avg_sq, step: torch.Tensor,
+                     tt_cores) -> None:
+    """In-place fused Adam / AdamW on the cores and both moments (no counterpart in the reference; an addition beside its
+    eleven functions).  ``step``: int32 [num_tables, 4] on the device, word 0 of a row = that table's steps so far
+    (``ttemb_native.new_adam_step`` per table).  Dense Adam: every row of a table with ids moves; a table without ids in
+    this call is left alone, like a call with ``nnz == 0``."""
+    if nnz == 0:
+        return
+    shape = _nat.make_shape(tt_p_shapes, tt_q_shapes, tt_ranks)
+    num_tables, B = tt_cores[0].shape[0], d_output.shape[-2]
+    d_output = d_output.contiguous().view(num_tables, B, D)
+    bounds = _table_bounds(tableidx, nnz, num_tables)
+    hp = _nat.make_adam(learning_rate, eps, (beta1, beta2), weight_decay, decoupled_weight_decay)
+    for k in range(num_tables):
+        lo, hi = bounds[k], bounds[k + 1]
+        if hi > lo:
+            _nat.backward_adam(shape, _nat.core_views(tt_cores, k), _nat.core_views(exp_avg, k), _nat.core_views(exp_avg_sq, k),
+                               step.view(-1, 4)[k], indices[lo:hi], rowidx[lo:hi], hi - lo, None, B, d_output[k], hp,
+                               _ws(d_output.device))
+
+
 def update_cache_state(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor) -> None:
     if indices.numel() == 0:
         return

@@ -7,6 +7,10 @@ table is replicated (it is < 10 MB), each rank looks up its own mini-batch in
 dense-gradient mode, and the tiny gradients are summed with ONE all-reduce (RCCL over
 xGMI with backend "nccl"; gloo on CPU in the tests) instead of one bucket per core.
 The 1/world averaging is folded into the learning rate.
+
+A module built with ``OptimType.ADAM`` is stepped by the fused Adam / AdamW epilogue instead (``ttemb_adam_step``): the
+summed gradient is scaled by 1/world BEFORE it enters the moments, the moments live in flat buffers the module's state
+buffers are views of, and the step count is the module's device word -- a deferred step carries no host state.
 """
 from __future__ import annotations
 
@@ -56,13 +60,22 @@ def default_apply(weight: torch.Tensor, grad: torch.Tensor, lr: float, skip: Opt
 
 
 class TTDataParallel:
-    """Wrap a dense-mode (``sparse=False``) TT module for data-parallel SGD.
+    """Wrap a dense-mode (``sparse=False``) TT module for data-parallel SGD -- or, for a module built with
+    ``optimizer=OptimType.ADAM``, data-parallel Adam / AdamW.
 
     The core gradients are produced by the backward kernels directly inside one flat bucket
     (no packing copy), summed with ONE all-reduce, and applied by ONE fused SGD launch over a
     flat weight buffer the cores are views of.  If a caller re-points ``tt_cores[t].data``
     (the reference's initialisers do, gnn_model.py:142-178) the step falls back to per-core
     launches until ``adopt_parameters()`` is called again.
+
+    An ``OptimType.ADAM`` module (every other optimiser value is stepped as SGD, as before) is stepped by the native Adam
+    epilogue on the device, ``ttemb_adam_step`` with the module's ``betas`` / ``eps`` / ``weight_decay``: there is no CPU
+    path and no injected ``apply_fn`` for it (the constructor asserts), one table only.  The moments live in two flat buffers
+    laid out like the weights; ``optimizer_state`` / ``optimizer_state_v`` of the module are re-pointed to views of them, so
+    the cores' moments and ``adam_step`` are in the module's ``state_dict``.  With a ``cache_weight`` in the bucket, ITS
+    moments exist only in ``flat_m`` / ``flat_v`` of this wrapper and are not part of any ``state_dict``.  Re-pointed cores
+    or state raise until ``adopt_parameters()`` is called again (no per-core fall-back).
     """
 
     def __init__(self, module, process_group: Optional[dist.ProcessGroup] = None,
@@ -84,6 +97,12 @@ class TTDataParallel:
         self._fault_dirty = True     # (the bucket's fault slot holds something other than 0)
         self._nat = None
         self._word_buf, self._word = None, None
+        self.adam = getattr(getattr(module, "optimizer", None), "value", None) == "adam"
+        if self.adam:
+            assert apply_fn is default_apply, "an OptimType.ADAM module is stepped by the native Adam epilogue (no apply_fn)"
+            assert module.num_tables == 1, "data-parallel Adam covers one table (one step count)"
+        self.flat_m: Optional[torch.Tensor] = None
+        self.flat_v: Optional[torch.Tensor] = None
         self.adopt_parameters()
         # the backward kernels write the core gradients straight into the bucket
         module._dense_grad_out = [v[0] if v.dim() == 3 and v.shape[0] == 1 else v
@@ -98,6 +117,15 @@ class TTDataParallel:
             for v, p in zip(self.weight_views, b.params):
                 v.copy_(p.data)
                 p.data = v
+            if self.adam:   # the moments in the same flat layout (a cache_weight's moments live in the flat buffers only)
+                self.flat_m, self.flat_v = torch.zeros_like(self.flat_weights), torch.zeros_like(self.flat_weights)
+                m = self.module
+                for flat, states in ((self.flat_m, m.optimizer_state), (self.flat_v, m.optimizer_state_v)):
+                    for t in range(self.n_cores):
+                        st = states[t]
+                        view = flat[b.offsets[t]:b.offsets[t] + b.sizes[t]].view_as(st)
+                        view.copy_(st)
+                        st.data = view
 
     def _flat_ok(self) -> bool:
         return all(p.data.data_ptr() == v.data_ptr() for p, v in zip(self.bucket.params, self.weight_views))
@@ -111,7 +139,9 @@ class TTDataParallel:
                     dist.broadcast(p.data, src, group=self.group)
 
     def step(self, lr: Optional[float] = None, overlap: bool = False) -> None:
-        """Call after ``loss.backward()``: all-reduce(sum) once, then w -= lr/world * g.
+        """Call after ``loss.backward()``: all-reduce(sum) once, then w -= lr/world * g -- for an ``OptimType.ADAM`` module
+        the Adam / AdamW step with learning rate ``lr`` on the gradient g / world (it is averaged before it enters the
+        moments), which advances the module's device step count unless the step is skipped.
 
         ``overlap=True`` only *starts* the all-reduce: waiting for it and the update are deferred to the moment the
         next ``forward`` needs the cores, i.e. after that forward's id-only work (grouping pass) has been enqueued --
@@ -167,11 +197,27 @@ class TTDataParallel:
             work.wait()
         b = self.bucket
         guard = (self._skip,) if self.apply_fn is default_apply else ()   # (an injected epilogue -- the CPU tests' -- takes no guard)
-        if self._flat_ok():
+        if self.adam:
+            self._adam_flush(lr)
+        elif self._flat_ok():
             self.apply_fn(self.flat_weights, b.flat[:b.n_grad], lr / self.world, *guard)
         else:
             for p, g in zip(b.params, b.views):
                 self.apply_fn(p.data, g, lr / self.world, *guard)
+
+    def _adam_flush(self, lr: float) -> None:
+        """The guarded Adam epilogue on the flat weights: g / world enters the moments; a non-zero skip word (some rank's
+        gradient came from a poisoned plan) leaves weights, moments and the step count alone."""
+        import ttemb_native as nat
+        m, b = self.module, self.bucket
+        states_ok = all(st.data_ptr() == self.flat_m[o:o + 1].data_ptr() for st, o in zip(m.optimizer_state, b.offsets)) and \
+            all(st.data_ptr() == self.flat_v[o:o + 1].data_ptr() for st, o in zip(m.optimizer_state_v, b.offsets))
+        if not (self._flat_ok() and states_ok):
+            raise RuntimeError("tt_cores / optimizer state were re-pointed after TTDataParallel adopted them: call "
+                               "adopt_parameters() again (the Adam epilogue runs on the flat buffers)")
+        hp = nat.make_adam(lr, float(m.eps), m.betas, m.weight_decay, m.decoupled_weight_decay)
+        nat.adam_step(self.flat_weights, self.flat_m, self.flat_v, m.adam_step[0], b.flat[:b.n_grad], hp,
+                      grad_scale=1.0 / self.world, skip=self._skip)
 
     def _poison_word(self) -> Optional[torch.Tensor]:
         """int32[1] view of the word the module's last grouped backward left in its workspace header, or None (CPU, or a

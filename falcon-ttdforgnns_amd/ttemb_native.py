@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_backward_dense_exact", "ttemb_backward_sgd_exact", "ttemb_backward_adagrad_exact",
     "ttemb_bag_workspace_bytes", "ttemb_bag_reduce", "ttemb_bag_reduce_backward", "ttemb_bag_mean",
     "ttemb_drop_padding_workspace_bytes", "ttemb_drop_padding", "ttemb_pad_weights",
+    "ttemb_backward_adam", "ttemb_backward_adam_window", "ttemb_backward_adam_exact", "ttemb_adam_step",
 )
 
 
@@ -45,6 +46,21 @@ class Shape(ctypes.Structure):
     """Mirror of ``ttemb_shape_t``."""
     _fields_ = [("T", ctypes.c_int32), ("p", ctypes.c_int32 * MAX_CORES),
                 ("q", ctypes.c_int32 * MAX_CORES), ("R", ctypes.c_int32 * (MAX_CORES + 1))]
+
+
+class AdamParams(ctypes.Structure):
+    """Mirror of ``ttemb_adam_t``: the hyper-parameters of the fused Adam / AdamW step."""
+    _fields_ = [("lr", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float),
+                ("decoupled", ctypes.c_int32), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double)]
+
+
+def make_adam(lr: float, eps: float, betas=(0.9, 0.999), weight_decay: float = 0.0, decoupled: bool = False) -> AdamParams:
+    return AdamParams(float(lr), float(eps), float(weight_decay), 1 if decoupled else 0, float(betas[0]), float(betas[1]))
+
+
+def new_adam_step(device) -> torch.Tensor:
+    """The device words of an Adam state (``ttemb_adam_t``'s ``step``): int32[4], word 0 = the steps applied so far."""
+    return torch.zeros(4, dtype=torch.int32, device=device)
 
 
 def make_shape(p: Sequence[int], q: Sequence[int], ranks: Sequence[int]) -> Shape:
@@ -124,6 +140,11 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_backward_dense_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_sgd_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, f32, vp, i64, vp, i64, vp]
     lib.ttemb_backward_adagrad_exact.argtypes = [shp, vp, vp, vp, vp, i64, i64, vp, f32, f32, vp, i64, vp, i64, vp]
+    adm = ctypes.POINTER(AdamParams)
+    lib.ttemb_backward_adam.argtypes = [shp, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, adm, vp, i64, vp, i64, vp]
+    lib.ttemb_backward_adam_window.argtypes = [shp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, adm, vp, i64, vp]
+    lib.ttemb_backward_adam_exact.argtypes = [shp, vp, vp, vp, vp, vp, vp, i64, i64, vp, adm, vp, i64, vp, i64, vp]
+    lib.ttemb_adam_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, adm, vp, vp]
     lib.ttemb_bag_workspace_bytes.restype = i64
     lib.ttemb_bag_workspace_bytes.argtypes = [i64, i64, i64]
     lib.ttemb_bag_reduce.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
@@ -400,6 +421,29 @@ def backward_adagrad(shape: Shape, cores, opt_state, indices, rowidx, nnz: int, 
                                           lr, eps, _ptr(w), w.numel(), *_plan_args(plan), _stream(d_output)))
 
 
+def backward_adam(shape: Shape, cores, exp_avg, exp_avg_sq, step: torch.Tensor, indices, rowidx, nnz: int, nnz_dev, B: int,
+                  d_output, hp: AdamParams, ws: Workspace, plan: Optional[torch.Tensor] = None,
+                  offsets: Optional[torch.Tensor] = None) -> None:
+    """Fused Adam / AdamW step (``ttemb_backward_adam``): ``exp_avg`` / ``exp_avg_sq`` shaped like the cores, ``step`` the
+    int32[4] device words of ``new_adam_step``."""
+    dev = d_output.device
+    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_backward_adam(ctypes.byref(shape), _ptr_array(cores), _ptr_array(exp_avg), _ptr_array(exp_avg_sq),
+                                       _ptr(step), _ptr(indices), _ptr(rowidx), _ptr(offsets), nnz, _ptr(nnz_dev), B,
+                                       _ptr(d_output), ctypes.byref(hp), _ptr(w), w.numel(), *_plan_args(plan),
+                                       _stream(d_output)))
+
+
+def adam_step(weights, exp_avg, exp_avg_sq, step: torch.Tensor, grads, hp: AdamParams, grad_scale: float = 1.0,
+              skip: Optional[torch.Tensor] = None) -> None:
+    """Flat Adam / AdamW epilogue (``ttemb_adam_step``): ``g = grads * grad_scale``; a non-zero device word ``skip[0]``
+    leaves weights, moments and the step count as they are."""
+    with _on_device(weights.device):
+        _check(LIB.ttemb_adam_step(_ptr(weights), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(step), _ptr(grads), weights.numel(),
+                                   grad_scale, ctypes.byref(hp), _ptr(skip), _stream(weights)))
+
+
 def sgd_step(weights: torch.Tensor, grads: torch.Tensor, lr: float) -> None:
     with _on_device(weights.device):
         _check(LIB.ttemb_sgd_step(_ptr(weights), _ptr(grads), weights.numel(), lr, _stream(weights)))
@@ -458,8 +502,9 @@ def forward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.T
 
 def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.Tensor, offsets: torch.Tensor, bag0: int, B: int,
                     d_output: torch.Tensor, ws: Workspace, d_cores: Optional[Sequence[torch.Tensor]] = None,
-                    opt_state: Optional[Sequence[torch.Tensor]] = None, lr: float = 0.0, eps: float = 0.0) -> None:
-    """``d_cores``: dense gradients of the window's table; else the fused step (Adagrad when ``opt_state`` is given)."""
+                    opt_state: Optional[Sequence[torch.Tensor]] = None, lr: float = 0.0, eps: float = 0.0, adam=None) -> None:
+    """``d_cores``: dense gradients of the window's table; else the fused step (Adagrad when ``opt_state`` is given; Adam
+    with ``adam = (exp_avg_sq, step, AdamParams)``, ``opt_state`` then the first moment)."""
     nnz, bags = indices.numel(), offsets.numel() - 1
     dev = d_output.device
     w = ws.get(window_workspace_bytes(shape, OP_BACKWARD, nnz, bags, B), dev)
@@ -468,6 +513,9 @@ def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.
     with _on_device(dev):
         if d_cores is not None:
             _check(LIB.ttemb_backward_dense_window(*head, *ids, _ptr_array(d_cores), _ptr(w), w.numel(), _stream(d_output)))
+        elif adam is not None:
+            _check(LIB.ttemb_backward_adam_window(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
+                                                  ctypes.byref(adam[2]), _ptr(w), w.numel(), _stream(d_output)))
         elif opt_state is None:
             _check(LIB.ttemb_backward_sgd_window(*head, *ids, lr, _ptr(w), w.numel(), _stream(d_output)))
         else:
@@ -514,18 +562,26 @@ def forward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Ten
 
 
 def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Tensor, B: int, d_output: torch.Tensor,
-                   ws: Workspace, d_cores=None, opt_state=None, lr: float = 0.0, eps: float = 0.0) -> None:
+                   ws: Workspace, d_cores=None, opt_state=None, lr: float = 0.0, eps: float = 0.0, adam=None) -> None:
     """Bit-reproducible backward: dense gradients into ``d_cores`` (every row written), else the fused step on the rows
-    the ids touch (Adagrad when ``opt_state`` is given)."""
+    the ids touch (Adagrad when ``opt_state`` is given), or dense Adam on every row with ``adam = (exp_avg_sq, step,
+    AdamParams)`` and ``opt_state`` the first moment."""
     nnz = indices.numel()
     dev = d_output.device
-    w = ws.get(exact_workspace_bytes(shape, nnz, B), dev)
+    need = exact_workspace_bytes(shape, nnz, B)
+    if adam is not None:   # + the gradient scratch behind it (include/ttemb.h, ttemb_backward_adam_exact)
+        need = -(-need // 256) * 256 + sum(-(-(shape.p[t] * shape.R[t] * shape.q[t] * shape.R[t + 1] * 4) // 256) * 256
+                                           for t in range(shape.T))
+    w = ws.get(need, dev)
     head = (ctypes.byref(shape), _ptr_array(cores))
     ids = (_ptr(indices), _ptr(offsets), nnz, B, _ptr(d_output))
     tail = (_ptr(w), w.numel(), None, 0, _stream(d_output))
     with _on_device(dev):
         if d_cores is not None:
             _check(LIB.ttemb_backward_dense_exact(*head, *ids, _ptr_array(d_cores), *tail))
+        elif adam is not None:
+            _check(LIB.ttemb_backward_adam_exact(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
+                                                 ctypes.byref(adam[2]), *tail))
         elif opt_state is None:
             _check(LIB.ttemb_backward_sgd_exact(*head, *ids, lr, *tail))
         else:
@@ -745,6 +801,7 @@ class LeanCalls:
         self.epoch = -1
         self.core_key, self.core_arr = None, None
         self.state_key, self.state_arr = None, None
+        self.state2_key, self.state2_arr = None, None   # (Adam: the second moment)
         self.grad_key, self.grad_arr = None, None
         self.grouped: dict = {}
 
@@ -830,7 +887,8 @@ class LeanCalls:
             g = self.grouped[(nnz, B)] = nnz > 0 and (kernel_family(self.shape, nnz, B, True) & 7) in (FAMILY_GROUPED, FAMILY_GROUPED_WIDE)
         return g
 
-    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan):
+    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan, adam=None):
+        """``adam = (exp_avg_sq, step, AdamParams)``: the fused Adam step, ``state`` then the first moment."""
         _, bwd_ws, plan_n = self._entry(nnz, B)
         self.core_key, self.core_arr = self._ptrs(cores, self.core_key, self.core_arr)
         dev = d_output.device
@@ -838,7 +896,13 @@ class LeanCalls:
         pp, pn = (plan.data_ptr(), plan_n) if plan is not None else (None, 0)
         ids = indices.data_ptr() if nnz else None
         with _on_device(dev):
-            if state is None:
+            if adam is not None:
+                self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
+                self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
+                rc = LIB.ttemb_backward_adam(self.shape_ref, self.core_arr, self.state_arr, self.state2_arr, adam[1].data_ptr(), ids,
+                                             None, offsets.data_ptr(), nnz, None, B, d_output.data_ptr() if B else None,
+                                             ctypes.byref(adam[2]), w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
+            elif state is None:
                 rc = LIB.ttemb_backward_sgd(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, None, B,
                                             d_output.data_ptr() if B else None, lr, w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
             else:

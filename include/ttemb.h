@@ -312,6 +312,44 @@ int ttemb_adagrad_step(float* weights, float* state, const float* grads, int64_t
                        float lr, float eps, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Fused Adam / AdamW (no counterpart in the reference: its OptimType.ADAM dispatches to Adagrad, tt_embeddings_ops.py:229-286;
+ * its drivers step the cores with torch.optim.Adam / AdamW).  DENSE Adam, as torch.optim.Adam(amsgrad=False) on the dense
+ * core gradients: every element of every core moves on every applied step, also rows no id of the call touches (their g is
+ * 0, their first moment is not).  Per element, t = the number of steps applied including this one:
+ *     g' = g + wd w  (decoupled = 0)   |   w = w - lr wd w  (decoupled = 1, AdamW; g' = g)
+ *     m = b1 m + (1 - b1) g' ;  v = b2 v + (1 - b2) g'^2 ;  w = w - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * (a zero denominator -- v = 0 and eps = 0 -- leaves w alone).  `exp_avg[t]` / `exp_avg_sq[t]`: m and v, shaped like cores[t].
+ * `step`: int32[4] on the device, owned by the caller, all zero before the first step: word 0 is t; words 1-3 are scratch
+ * of the call (t + 1 and the two bias corrections as float bits, formed on the device by one lane of a kernel of the same
+ * call).  t lives on the device so that a captured graph and a deferred data-parallel step carry no host state; it advances
+ * once per applied step.  A call without ids (nnz = 0) is a no-op and does not advance t.  A step that is SKIPPED (a grouped
+ * call on a poisoned plan whose fault the host hears of, see "Device-side faults"; the `skip` word of ttemb_adam_step) leaves
+ * w, m, v and t as they were.  On the grouped route of a one-piece call the step rides in the last backward kernel (no
+ * launch added); every other route writes the gradient into the workspace and steps all cores in one launch behind a
+ * one-lane launch that forms the pending step words.
+ * ------------------------------------------------------------------------------- */
+typedef struct ttemb_adam {
+  float lr, eps, weight_decay;
+  int32_t decoupled;      /* 0: torch.optim.Adam's coupled decay, 1: AdamW's */
+  double beta1, beta2;    /* in [0, 1); double: the bias corrections are formed from them */
+} ttemb_adam_t;
+int ttemb_backward_adam(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                        int32_t* step, const int64_t* indices, const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
+                        const int32_t* nnz_dev, int64_t B, const float* d_output, const ttemb_adam_t* hp,
+                        void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream);
+/* one table of a table-batched call (see "A WINDOW of a longer id list"); `step` is that table's.  A window that turns out
+ * empty on the device is a step on a zero gradient (m and v decay, t advances), what torch.optim.Adam does with it. */
+int ttemb_backward_adam_window(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                               int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total,
+                               int64_t bag0, int64_t B, const float* d_output, const ttemb_adam_t* hp, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+/* Flat epilogue over n floats (the data-parallel step): g = grads[i] * grad_scale (1 / world: the averaged gradient enters
+ * m and v), then the step above.  `skip`: null, or a 32-bit device word tested bit-wise as in ttemb_sgd_step_guarded:
+ * non-zero leaves weights, exp_avg, exp_avg_sq and step[0] untouched.  Buffers 16-byte aligned. */
+int ttemb_adam_step(float* weights, float* exp_avg, float* exp_avg_sq, int32_t* step, const float* grads, int64_t n,
+                    float grad_scale, const ttemb_adam_t* hp, const float* skip, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * LFU hash-table cache.
  * update_cache_state (tt_embeddings.cpp:144, tt_embeddings_cuda.cu:1083-1119):
  * insert every id with count+1 (Murmur3-style hash, <=3 linear probes, 64-bit CAS;
@@ -445,6 +483,14 @@ int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores
                                  const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
                                  const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes,
                                  const void* plan, int64_t plan_bytes, void* stream);
+/* Adam in exact mode (see "Fused Adam / AdamW"): ttemb_backward_dense_exact into scratch, then the flat step core by core --
+ * an elementwise step has no order, so cores, exp_avg and exp_avg_sq are a function of the inputs only.  Unlike the exact
+ * SGD / Adagrad steps it moves EVERY row (dense Adam).  Workspace: ttemb_exact_workspace_bytes() PLUS, behind it, the
+ * gradient scratch: the sum over the table's cores of their bytes, each rounded up to 256. */
+int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                              int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
+                              const float* d_output, const ttemb_adam_t* hp, void* workspace, int64_t workspace_bytes,
+                              const void* plan, int64_t plan_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Weighted and mean bags (torch.nn.functional.embedding_bag with include_last_offset=True: mode "sum" with
