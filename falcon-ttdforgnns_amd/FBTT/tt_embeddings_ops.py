@@ -539,6 +539,31 @@ class _BagMean(torch.autograd.Function):
         return d_sums, None
 
 
+class _BagMax(torch.autograd.Function):
+    """``mode="max"``: ``out[b][d] = max_{i in bag b} rows[i][d]`` over the looked-up rows of bags of one (``ttemb_bag_max``),
+    the first position winning among equal values and a NaN over every number.  Only the winners (int32 ``[B, D]``
+    positions) are kept, not ``rows``: the backward hands ``d_rows[i][d] = dOut[bag(i)][d]`` at the winner, zeros elsewhere
+    (every element written), to the lookup's own backward -- fused step, dense gradients, bucket, exact: whatever produced
+    ``rows``.  ``indices`` / ``pad``: positions whose id is the pad are skipped (the small-call route of a padded call)."""
+
+    @staticmethod
+    def forward(ctx, rows: torch.Tensor, offsets: torch.Tensor, module: "TableBatchedTTEmbeddingBag",
+                indices: Optional[torch.Tensor], pad: int) -> torch.Tensor:
+        B, D = offsets.numel() - 1, rows.shape[1]
+        out = torch.empty((B, D), dtype=torch.float32, device=rows.device)
+        argmax = torch.empty((B, D), dtype=torch.int32, device=rows.device)
+        _nat.bag_max(rows, offsets, out, argmax, module._ws, indices, pad)
+        ctx.offsets, ctx.argmax, ctx.nnz = offsets, argmax, rows.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        d_output = _aligned(d_output)
+        d_rows = torch.empty((ctx.nnz, d_output.shape[-1]), dtype=torch.float32, device=d_output.device)
+        _nat.bag_max_backward(d_output, ctx.argmax, ctx.offsets, d_rows)
+        return d_rows, None, None, None, None
+
+
 class _PadWeights(torch.autograd.Function):
     """The masked-rows route of a padded call: ``w'[i] = keep[i] (w[i] or 1) (1 / len'(bag(i)) for a mean)``
     (``ttemb_pad_weights``), the weights ``_WeightedBag`` then pools the bags-of-one rows with.  ``w`` is only given with
@@ -695,6 +720,12 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     ``mode="sum"`` with ``w`` (float32 ``[nnz]``) pools ``w[i] * row(indices[i])``, ``mode="mean"`` divides each bag sum by
     the bag's length (an empty bag gives zeros).  Weights with ``mode="mean"`` raise ``ValueError``.  Gradients reach the
     cores through every optimiser mode, and ``w.grad`` when ``w`` requires it.
+
+    ``forward(..., mode="max")`` (keyword-only, per call, where ``embedding_bag`` takes it) gives the element-wise maximum
+    of each bag's rows -- the first position wins among equal values, a NaN in any kept position makes the element NaN, an
+    empty bag gives zeros -- and sends each gradient element to the winner alone; it takes no ``per_sample_weights``.
+    ``mode="sum"`` / ``"mean"`` per call run what a module constructed with that mode runs, ``None`` the constructor's mode
+    (the constructor itself takes "sum" and "mean" only).  DESIGN.md §4.10.
 
     ``padding_idx`` (keyword-only; negative counts from the end) follows ``embedding_bag``'s: ids equal to it add nothing to
     their bag, are not counted in a mean and send no gradient (``full_weight()[padding_idx]`` is not zero: a TT table has no
@@ -1137,9 +1168,77 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             out = torch.stack(outs, 0)
         return out.unsqueeze(0) if tables_dim and T == 1 else out
 
+    def _max_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, exact: bool) -> torch.Tensor:
+        """``mode="max"`` on one table.  One row per id (the lookup of bags of one, whichever bridge serves it), then
+        ``_BagMax``.  With ``padding_idx``: where ``_pad_route`` answers "partition", the pad ids are dropped first and only
+        the kept ids are looked up (row-index form, the kept count stays on the device); else every id is looked up and
+        ``_BagMax`` skips the pad positions."""
+        nnz, B, dev = indices.numel(), offsets.numel() - 1, indices.device
+        pad = self.padding_idx
+        ones = self._bags_of_one(nnz, dev)
+        if pad is None:
+            return _BagMax.apply(self._lookup_one_table(table, nnz, indices, ones, exact), offsets, self, None, 0)
+        route = self._last_pad_route = self._pad_route(nnz, B, False, exact)
+        if route == "partition":
+            ids = torch.empty_like(indices)
+            bags = torch.empty_like(indices)   # (the bags of the kept ids: not needed, the rows are looked up one per id)
+            offs = torch.empty(B + 1, dtype=torch.int64, device=dev)
+            kept = torch.empty(1, dtype=torch.int32, device=dev)
+            _nat.drop_padding(indices, offsets, pad, ids, bags, offs, kept, self._ws)
+            # kept id i -> row i of the rows buffer; the rows past the kept count have no writer and no reader (`offs` ends
+            # at the kept count)
+            rows = TTLookupFunction.apply(self, table, nnz, ids, ones[:nnz], ones, kept, None, None, *self.tt_cores)
+            return _BagMax.apply(rows, offs, self, None, 0)
+        return _BagMax.apply(self._lookup_one_table(table, nnz, indices, ones, exact), offsets, self, indices, pad)
+
+    def _max_pooled(self, indices: torch.Tensor, offsets: torch.Tensor, tables_dim: bool) -> torch.Tensor:
+        """``forward(..., mode="max")`` (1-D ids and their offsets by now)."""
+        if not indices.is_cuda:
+            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
+        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
+        assert (offsets.numel() - 1) % self.num_tables == 0
+        T, B = self.num_tables, (offsets.numel() - 1) // self.num_tables
+        if not self._fused_probe():
+            self.update_cache(indices)
+        exact = self._exact_active()
+        if T == 1:
+            out = self._max_one_table(0, indices, offsets, exact)
+        elif B == 0:
+            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=indices.device)
+        else:
+            # several tables: the id list is split on the host (one synchronisation), as for weighted calls
+            bounds = offsets[:: B].tolist()
+            outs = []
+            for k in range(T):
+                lo, hi = int(bounds[k]), int(bounds[k + 1])
+                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
+                outs.append(self._max_one_table(k, indices[lo:hi].contiguous(), offs_k, exact))
+            out = torch.stack(outs, 0)
+        return out.unsqueeze(0) if tables_dim and T == 1 else out
+
+    def _per_call_mode(self, mode: str, indices: torch.Tensor, offsets: Optional[torch.Tensor],
+                       weights: Optional[torch.Tensor], tables_dim: bool) -> torch.Tensor:
+        """``forward(..., mode=...)``: "sum" / "mean" run what a module constructed with that mode runs; "max" the max bags."""
+        if mode not in ("sum", "mean", "max"):
+            raise ValueError(f"mode must be 'sum', 'mean' or 'max', got {mode!r}")
+        if mode == "max":
+            if weights is not None:
+                raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
+                                 "(as in torch.nn.functional.embedding_bag)")
+            if offsets is None or indices.dim() != 1:
+                indices, offsets, _ = self._fixed_bags(indices, offsets, None)
+            return self._max_pooled(indices, offsets, tables_dim)
+        own, self.mode = self.mode, mode   # (read while the call is routed only: no autograd node looks at it later)
+        try:
+            return self.forward(indices, offsets, per_sample_weights=weights)
+        finally:
+            self.mode = own
+
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
-                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                per_sample_weights: Optional[torch.Tensor] = None, mode: Optional[str] = None) -> torch.Tensor:
         # `warmup` is accepted and ignored, like the reference (it reads self.warmup, :862)
+        if mode is not None:
+            return self._per_call_mode(mode, indices, offsets, per_sample_weights, True)
         if offsets is None or indices.dim() != 1:
             indices, offsets, per_sample_weights = self._fixed_bags(indices, offsets, per_sample_weights)
         if self.padding_idx is not None:
@@ -1194,7 +1293,9 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                          decoupled_weight_decay=decoupled_weight_decay)
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
-                per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+                per_sample_weights: Optional[torch.Tensor] = None, mode: Optional[str] = None) -> torch.Tensor:
+        if mode is not None:
+            return self._per_call_mode(mode, indices, offsets, per_sample_weights, False)
         # same result as the reference's ``super().forward(...)[0]`` (:960-965) without the
         # [1, B, D] view: selecting table 0 would cost a zero-fill + copy of B*D floats in backward
         if offsets is None or indices.dim() != 1:

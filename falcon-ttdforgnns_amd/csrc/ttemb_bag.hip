@@ -7,6 +7,10 @@
 //              (bag_partial_kernel writes one partial per chunk it reaches) and its partials are added in chunk order.
 //   backward   d_rows[i] = w[i] dOut[bag(i)] and d_w[i] = <dOut[bag(i)], rows[i]> in one pass, one lane group per id.
 //   mean       dst[b] = src[b] / len(b), zeros for an empty bag.
+//   max        out[b][d] = max_{i in bag b} rows[i][d] and argmax[b][d] = the FIRST position that holds it (-1 without one);
+//              a NaN in a kept position wins over every number (the first NaN position).  Long bags go through the same
+//              fixed chunks as the sums: per chunk the partial (value, position), combined in chunk order by the same
+//              strict rule, so the first position still wins.  The backward sends dOut[b][d] to that position alone.
 //
 // Every kernel is deterministic by construction, in the sense of the exact-mode contract: no float atomics, no waits
 // between workgroups, grid-stride loops over work items (the grid decides who computes a value, never how), summation
@@ -23,6 +27,7 @@ namespace bag {
 constexpr int kBagNT = 256;               // threads per workgroup
 constexpr int64_t kBagChunk = 512;        // ids per chunk of a long bag
 constexpr int64_t kBagHeader = kFast3HeaderBytes;   // the workspace header of the grouped lookups: never written here
+constexpr int64_t kBagMaxIds = 0x7fffffff;   // max bags keep their winners as int32 positions
 
 struct Groups {
   int shift;   // log2(W)
@@ -203,6 +208,129 @@ __global__ __launch_bounds__(kBagNT) void pad_weights_kernel(const int64_t* __re
     w_out[j < first ? j : last + (j - first)] = 0.0f;
 }
 
+// ---- max bags ------------------------------------------------------------------------------------------------------------
+// The winner of a (bag, column) so far: its value and its position in the id list (p < 0: none yet).  `take` is the whole
+// rule: the first kept position is taken, then only a strictly larger value, or the first NaN over a number.
+struct Best4 {
+  float4 v;
+  int4 p;
+};
+
+__device__ __forceinline__ void max_take(float& best, int& pos, float v, int i) {
+  const bool take = pos < 0 || v > best || (v != v && best == best);
+  best = take ? v : best;
+  pos = take ? i : pos;
+}
+
+__device__ __forceinline__ void max_take4(Best4& b, float4 v, int4 p) {
+  if (p.x >= 0) max_take(b.v.x, b.p.x, v.x, p.x);
+  if (p.y >= 0) max_take(b.v.y, b.p.y, v.y, p.y);
+  if (p.z >= 0) max_take(b.v.z, b.p.z, v.z, p.z);
+  if (p.w >= 0) max_take(b.v.w, b.p.w, v.w, p.w);
+}
+
+__device__ __forceinline__ Best4 best_none() { return Best4{make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_int4(-1, -1, -1, -1)}; }
+
+// the winners of column c over positions [a, e) in position order; with `indices`, positions whose raw id is `pad` are skipped
+__device__ __forceinline__ Best4 max_walk(const float4* __restrict__ rows, const int64_t* __restrict__ indices, int64_t pad,
+                                          int64_t D4, int64_t c, int64_t a, int64_t e) {
+  Best4 b = best_none();
+#pragma unroll 4
+  for (int64_t i = a; i < e; ++i) {
+    if (indices != nullptr && indices[i] == pad) continue;
+    const int n = (int)i;
+    max_take4(b, rows[i * D4 + c], make_int4(n, n, n, n));
+  }
+  return b;
+}
+
+// As bag_partial_kernel: the part of every LONG bag that lies in chunk k goes to one of the chunk's two slots, here as the
+// partial winners (values in pv, positions in pp; a part of pads only leaves positions of -1).
+__global__ __launch_bounds__(kBagNT) void bag_max_partial_kernel(const float4* __restrict__ rows, const int64_t* __restrict__ indices,
+                                                                 int64_t pad, const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                 int64_t B, int64_t D4, int shift, int64_t nchunks,
+                                                                 float4* __restrict__ pv, int4* __restrict__ pp) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
+    const int64_t s = k * kBagChunk, e = s + kBagChunk < nnz ? s + kBagChunk : nnz;
+    const int64_t bs = bag_of_position(offsets, B, s), be = bag_of_position(offsets, B, e - 1);
+    for (int which = 0; which < 2; ++which) {
+      const int64_t b = which == 0 ? bs : be;
+      if (which == 1 && be == bs) break;
+      int64_t n0, n1;
+      bag_range(offsets, nnz, b, n0, n1);
+      const int64_t a = n0 > s ? n0 : s, z = n1 < e ? n1 : e;
+      if (n1 - n0 <= kBagChunk || a >= z) continue;
+      const int64_t slot = (2 * k + (n0 < s ? 0 : 1)) * D4;
+      for (int64_t c = lane; c < D4; c += W) {
+        const Best4 w = max_walk(rows, indices, pad, D4, c, a, z);
+        pv[slot + c] = w.v;
+        pp[slot + c] = w.p;
+      }
+    }
+  }
+}
+
+// out[b] and argmax[b]: a short bag is one walk in position order (a bag of one a copy); a long bag the combination of its
+// chunk partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); without a winner
+// (an empty bag, a bag of pads only) zeros and -1.
+__global__ __launch_bounds__(kBagNT) void bag_max_kernel(const float4* __restrict__ rows, const int64_t* __restrict__ indices,
+                                                         int64_t pad, const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                         int64_t D4, int shift, const float4* __restrict__ pv,
+                                                         const int4* __restrict__ pp, float4* __restrict__ out,
+                                                         int4* __restrict__ argmax) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
+    int64_t n0, n1;
+    bag_range(offsets, nnz, b, n0, n1);
+    const bool is_long = n1 - n0 > kBagChunk;
+    const int64_t k0 = n0 / kBagChunk, k1 = is_long ? (n1 - 1) / kBagChunk : k0;
+    for (int64_t c = lane; c < D4; c += W) {
+      Best4 w;
+      if (is_long) {
+        w = Best4{pv[(2 * k0 + 1) * D4 + c], pp[(2 * k0 + 1) * D4 + c]};
+        for (int64_t k = k0 + 1; k <= k1; ++k) max_take4(w, pv[2 * k * D4 + c], pp[2 * k * D4 + c]);
+      } else {
+        w = max_walk(rows, indices, pad, D4, c, n0, n1);
+      }
+      out[b * D4 + c] = make_float4(w.p.x < 0 ? 0.0f : w.v.x, w.p.y < 0 ? 0.0f : w.v.y, w.p.z < 0 ? 0.0f : w.v.z,
+                                    w.p.w < 0 ? 0.0f : w.v.w);
+      argmax[b * D4 + c] = w.p;
+    }
+  }
+}
+
+// d_rows[i][d] = dOut[bag(i)][d] where position i is the winner of (bag(i), d), else 0; every element is written (zeros for
+// a position outside every bag).  One lane group per id.
+__global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* __restrict__ d_out, const int4* __restrict__ argmax,
+                                                                  const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                  int64_t D4, int shift, float4* __restrict__ d_rows) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  const int64_t first = offsets[0], last = offsets[B];
+  for (int64_t i = (int64_t)blockIdx.x * per_block + g; i < nnz; i += (int64_t)gridDim.x * per_block) {
+    const bool in_bag = i >= first && i < last;
+    const int64_t b = in_bag ? bag_of_position(offsets, B, i) : 0;
+    const int n = (int)i;
+    for (int64_t c = lane; c < D4; c += W) {
+      float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (in_bag) {
+        const int4 p = argmax[b * D4 + c];
+        if (p.x == n || p.y == n || p.z == n || p.w == n) {
+          const float4 gv = d_out[b * D4 + c];
+          d = make_float4(p.x == n ? gv.x : 0.0f, p.y == n ? gv.y : 0.0f, p.z == n ? gv.z : 0.0f, p.w == n ? gv.w : 0.0f);
+        }
+      }
+      d_rows[i * D4 + c] = d;
+    }
+  }
+}
+
 int64_t chunks_of(int64_t nnz) { return (nnz + kBagChunk - 1) / kBagChunk; }
 
 unsigned grid_of(int64_t items, const Groups& gr) { return exact::ex_grid((items + gr.per_block - 1) / gr.per_block); }
@@ -291,6 +419,63 @@ int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t
   hipLaunchKernelGGL(bag_mean_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, reinterpret_cast<const float4*>(src),
                      reinterpret_cast<float4*>(dst), offsets, B, D / 4, gr.shift);
   return check_hip(hipGetLastError(), "bag_mean_kernel");
+}
+
+int64_t ttemb_bag_max_workspace_bytes(int64_t nnz, int64_t B, int64_t D) {
+  int rc = check_sizes("ttemb_bag_max_workspace_bytes", nnz, B, D);
+  if (rc) return rc;
+  // per chunk two slots of D values and D positions
+  return kBagHeader + 2 * chunks_of(nnz) * D * (int64_t)(sizeof(float) + sizeof(int32_t));
+}
+
+int ttemb_bag_max(const float* rows, const int64_t* indices, int64_t pad, const int64_t* offsets, int64_t nnz, int64_t B,
+                  int64_t D, float* output, int32_t* argmax, void* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes("ttemb_bag_max", nnz, B, D);
+  if (rc) return rc;
+  if (nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "ttemb_bag_max: nnz = %lld does not fit the int32 positions", (long long)nnz);
+  if (B == 0) return TTEMB_OK;
+  if (offsets == nullptr || output == nullptr || argmax == nullptr)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_max: offsets / output / argmax is null");
+  if (nnz > 0 && rows == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_max: rows is null");
+  if (misaligned(rows) || misaligned(output) || misaligned(argmax))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_max: rows / output / argmax not 16-byte aligned");
+  const int64_t need = ttemb_bag_max_workspace_bytes(nnz, B, D);
+  if (workspace_bytes < need || workspace == nullptr)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_max: workspace of %lld bytes, need %lld", (long long)workspace_bytes, (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4, nch = chunks_of(nnz);
+  const Groups gr = groups_of(D4);
+  float4* pv = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
+  int4* pp = reinterpret_cast<int4*>(pv + 2 * nch * D4);
+  const float4* r4 = reinterpret_cast<const float4*>(rows);
+  if (nch > 0) {
+    hipLaunchKernelGGL(bag_max_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz, B, D4,
+                       gr.shift, nch, pv, pp);
+    if ((rc = check_hip(hipGetLastError(), "bag_max_partial_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(bag_max_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz, B, D4, gr.shift,
+                     pv, pp, reinterpret_cast<float4*>(output), reinterpret_cast<int4*>(argmax));
+  return check_hip(hipGetLastError(), "bag_max_kernel");
+}
+
+int ttemb_bag_max_backward(const float* d_output, const int32_t* argmax, const int64_t* offsets, int64_t nnz, int64_t B,
+                           int64_t D, float* d_rows, void* stream) {
+  int rc = check_sizes("ttemb_bag_max_backward", nnz, B, D);
+  if (rc) return rc;
+  if (nnz > kBagMaxIds)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_max_backward: nnz = %lld does not fit the int32 positions", (long long)nnz);
+  if (nnz == 0) return TTEMB_OK;
+  if (offsets == nullptr || d_rows == nullptr || (B > 0 && (d_output == nullptr || argmax == nullptr)))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_max_backward: offsets / d_rows / d_output / argmax is null");
+  if (misaligned(d_output) || misaligned(argmax) || misaligned(d_rows))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_max_backward: d_output / argmax / d_rows not 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4;
+  const Groups gr = groups_of(D4);
+  hipLaunchKernelGGL(bag_max_backward_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st,
+                     reinterpret_cast<const float4*>(d_output), reinterpret_cast<const int4*>(argmax), offsets, nnz, B, D4,
+                     gr.shift, reinterpret_cast<float4*>(d_rows));
+  return check_hip(hipGetLastError(), "bag_max_backward_kernel");
 }
 
 int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,

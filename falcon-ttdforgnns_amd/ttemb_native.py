@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_bag_workspace_bytes", "ttemb_bag_reduce", "ttemb_bag_reduce_backward", "ttemb_bag_mean",
     "ttemb_drop_padding_workspace_bytes", "ttemb_drop_padding", "ttemb_pad_weights",
     "ttemb_backward_adam", "ttemb_backward_adam_window", "ttemb_backward_adam_exact", "ttemb_adam_step",
+    "ttemb_bag_max_workspace_bytes", "ttemb_bag_max", "ttemb_bag_max_backward",
 )
 
 
@@ -150,6 +151,10 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_bag_reduce.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
     lib.ttemb_bag_reduce_backward.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]
     lib.ttemb_bag_mean.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.ttemb_bag_max_workspace_bytes.restype = i64
+    lib.ttemb_bag_max_workspace_bytes.argtypes = [i64, i64, i64]
+    lib.ttemb_bag_max.argtypes = [vp, vp, i64, vp, i64, i64, i64, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_max_backward.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
     lib.ttemb_drop_padding_workspace_bytes.restype = i64
     lib.ttemb_drop_padding_workspace_bytes.argtypes = [i64, i64]
     lib.ttemb_drop_padding.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]
@@ -158,7 +163,7 @@ def _load() -> ctypes.CDLL:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
                         "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
-                        "ttemb_drop_padding_workspace_bytes"):
+                        "ttemb_drop_padding_workspace_bytes", "ttemb_bag_max_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -649,6 +654,51 @@ def bag_mean(src: torch.Tensor, dst: torch.Tensor, offsets: torch.Tensor) -> Non
     _check_sizes((src, dst), B * D)
     with _on_device(dst.device):
         _check(LIB.ttemb_bag_mean(_ptr(src), _ptr(dst), _ptr(offsets), B, D, _stream(dst)))
+
+
+def bag_max_workspace_bytes(nnz: int, B: int, D: int) -> int:
+    """Bytes ``bag_max`` needs (behind the lookups' 40 KB header, as ``bag_workspace_bytes``)."""
+    key = ("bagmax", nnz, B, D)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_bag_max_workspace_bytes(nnz, B, D))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def bag_max(rows: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, argmax: torch.Tensor, ws: Workspace,
+            indices: Optional[torch.Tensor] = None, pad: int = 0) -> None:
+    """``output[b][d] = max_{i in bag b} rows[i][d]``, ``argmax[b][d]`` (int32) the first position that holds it, -1 and zeros
+    without one (``ttemb_bag_max``).  With ``indices``, positions whose id equals ``pad`` are skipped."""
+    nnz, D = rows.shape
+    B = offsets.numel() - 1
+    _check_sizes((rows,), nnz * D)
+    _check_sizes((output,), B * D)
+    if argmax.dtype != torch.int32 or argmax.numel() != B * D:
+        raise ValueError(f"bag_max: output / argmax must hold [{B}, {D}] float32 / int32")
+    if indices is not None and (indices.dtype != torch.int64 or indices.numel() != nnz):
+        raise ValueError(f"bag_max: indices must be int64 [{nnz}]")
+    dev = output.device
+    w = ws.get(bag_max_workspace_bytes(nnz, B, D), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_bag_max(_ptr(rows), _ptr(indices), int(pad), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(argmax),
+                                 _ptr(w), w.numel(), _stream(output)))
+
+
+def bag_max_backward(d_output: torch.Tensor, argmax: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor) -> None:
+    """``d_rows[i][d] = d_output[bag(i)][d]`` where ``argmax[bag(i)][d] == i``, else 0; every element written
+    (``ttemb_bag_max_backward``)."""
+    nnz, D = d_rows.shape
+    B = offsets.numel() - 1
+    _check_sizes((d_output,), B * D)
+    _check_sizes((d_rows,), nnz * D)
+    if argmax.dtype != torch.int32 or argmax.numel() != B * D:
+        raise ValueError(f"bag_max_backward: argmax must hold [{B}, {D}] int32")
+    with _on_device(d_rows.device):
+        _check(LIB.ttemb_bag_max_backward(_ptr(d_output), _ptr(argmax), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                          _stream(d_rows)))
 
 
 def drop_padding_workspace_bytes(nnz: int, B: int) -> int:

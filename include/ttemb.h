@@ -521,6 +521,36 @@ int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const
 int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t B, int64_t D, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Max bags (torch.nn.functional.embedding_bag's mode "max", include_last_offset=True).  As the weighted sum: look the ids
+ * up as nnz bags of one, then pool the rows here; no core is read (ttemb_bag.hip).
+ *   - ttemb_bag_max: output[b][d] = max over the kept positions i of bag b of rows[i][d], and argmax[b][d] (int32) = the
+ *     FIRST position of this call's id list that holds it: walking the bag in position order a later position wins only
+ *     with a strictly larger value, so of equal values (+0.0 and -0.0 are equal) the earlier position stays.  NaN is never
+ *     swallowed: a NaN in any kept position makes the element NaN and the winner is the first NaN position
+ *     (take = v > best || (v != v && best == best)); torch's CPU kernel keeps a NaN only when it comes first.  A bag
+ *     without a kept position (empty, or pads only) gives zeros and argmax -1.  `indices` (nullable): when given, a
+ *     position whose raw id indices[i] equals `pad` is not kept (embedding_bag's padding_idx); NULL keeps every position
+ *     and `pad` is ignored.
+ *   - ttemb_bag_max_backward: d_rows[i][d] = d_output[bag(i)][d] where argmax[bag(i)][d] == i, else 0.  EVERY element of
+ *     d_rows[nnz][D] is written -- zeros for pads and for positions outside every bag -- so no zero-fill pass is needed, and
+ *     any lookup backward then takes d_rows with the same bags of one.
+ * rows / d_rows are float32 [nnz][D], output / d_output float32 [B][D], argmax int32 [B][D], offsets int64 [B + 1] over the
+ * concatenated bags.  D is a positive multiple of 4, the [.][D] buffers are 16-byte aligned, nnz < 2^31 (the positions are
+ * int32); checks and error codes as the sum calls.  Deterministic by construction, as exact mode: no float atomics, no
+ * waits between workgroups, grid-stride loops whose grid is capped by ttemb_set_exact_grid.  A bag of more than 512 ids is
+ * cut into the fixed chunks [512 k, 512 (k + 1)) of the position list; their partial (value, position) pairs (workspace)
+ * are combined in chunk order by the same strict rule, so the first position still wins.  Every workspace word that is read
+ * was written earlier in the same call.  ttemb_bag_max_workspace_bytes sizes the workspace of ttemb_bag_max; it lies behind
+ * the 40 KB header, so the workspace of the lookups serves it too.  No host synchronisation and no allocation.
+ * ------------------------------------------------------------------------------- */
+int64_t ttemb_bag_max_workspace_bytes(int64_t nnz, int64_t B, int64_t D);
+int ttemb_bag_max(const float* rows, const int64_t* indices /* NULL: no padding */, int64_t pad, const int64_t* offsets,
+                  int64_t nnz, int64_t B, int64_t D, float* output, int32_t* argmax, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+int ttemb_bag_max_backward(const float* d_output, const int32_t* argmax, const int64_t* offsets, int64_t nnz, int64_t B,
+                           int64_t D, float* d_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Padding (torch.nn.functional.embedding_bag's padding_idx: an id equal to `pad` -- compared with the raw id, before any
  * clamping of invalid ids -- adds nothing to its bag, is not counted in a mean and sends no gradient).  Two routes:
  *   - ttemb_drop_padding: a stable flagged partition of indices[0:nnz].  The kept ids -- inside a bag of `offsets`
