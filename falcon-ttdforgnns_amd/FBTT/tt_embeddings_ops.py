@@ -604,6 +604,27 @@ class _ReplayLookup(torch.autograd.Function):
         return None, None
 
 
+class _ReplayVariableLookup(torch.autograd.Function):
+    """Autograd node of a ``capture(..., variable=True)`` call of ``n_live`` ids in ``B_live`` bags, already staged: the
+    forward replays and hands out the live rows of the static output; the backward fills the live rows of the static
+    gradient -- the rows past them belong to empty bags, which no kernel reads -- and replays, unless the call had no id."""
+
+    @staticmethod
+    def forward(ctx, anchor: torch.Tensor, cap: "CapturedLookup", n_live: int, B_live: int) -> torch.Tensor:
+        ctx.cap, ctx.n_live, ctx.B_live = cap, n_live, B_live
+        cap.fwd_graph.replay()
+        return cap.output[:B_live]
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        if ctx.n_live == 0:   # a call without ids is a no-op for every optimiser and does not advance Adam's t (include/ttemb.h)
+            return None, None, None, None
+        cap = ctx.cap
+        cap.d_output[:ctx.B_live].copy_(d_output)
+        cap.bwd_graph.replay()
+        return None, None, None, None
+
+
 class CapturedLookup:
     """``emb.capture(nnz, B)``: a lookup of fixed size whose forward and whose backward (gradient + fused optimiser step)
     are each ONE HIP-graph replay -- for steps so small that Python and launch overhead are most of their time (the metric's
@@ -611,18 +632,43 @@ class CapturedLookup:
     ``out = cap(indices[, offsets])``; ``out`` is a static buffer that the next call overwrites (as with
     ``torch.cuda.make_graphed_callables``).  The workspace and plan the graphs were captured with are owned by this object,
     so other calls on the module cannot move them.  ``sparse=True`` modules with one table and no live cache.  A captured
-    lookup is the unweighted ``mode="sum"`` call: it takes no ``per_sample_weights``, and a ``mode="mean"`` module is refused."""
+    lookup is the unweighted ``mode="sum"`` call: it takes no ``per_sample_weights``, and a ``mode="mean"`` module is refused.
 
-    def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, offsets: Optional[torch.Tensor] = None) -> None:
+    ``variable=True``: ``nnz`` and ``B`` are CAPACITIES and every call brings its own size -- any ``indices.numel() <= nnz`` in
+    ``offsets.numel() - 1 <= B`` bags (without offsets: bags of one id), int64 or int32 -- which is what a GNN's frontiers
+    need.  One launch (``ttemb_stage_call``) puts the call into the static buffers, pads the offsets with empty bags and
+    leaves the id count in a device word the captured kernels read; the result is ``output[:B_live]``, a view of the static
+    buffer.  The launches are sized by the capacity, so pick one near the largest frontier.  Offsets come with each call,
+    none at capture.  Not in exact mode: the exact backward takes no device id count.  DESIGN.md §4.11."""
+
+    def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, offsets: Optional[torch.Tensor] = None,
+                 variable: bool = False) -> None:
         assert module.sparse and module.num_tables == 1, "capture() covers the fused-optimiser mode of a single table"
         assert not (module.use_cache and not module.warmup), "capture() with a live row cache is not supported"
         assert module.mode == "sum", "capture() covers mode='sum' (unweighted)"
         assert module.padding_idx is None, "capture() does not cover padding_idx: capture a module without it"
         self.module, self.nnz, self.B = module, int(nnz), int(B)
+        self.variable = bool(variable)
+        if self.variable and offsets is not None:
+            raise ValueError("capture(variable=True) takes no offsets: nnz and B are capacities, the offsets come with each call")
+        if self.variable and not (0 < self.nnz < 2 ** 31 and self.B > 0):
+            raise ValueError(f"capture(variable=True): the capacities must be positive (ids below 2^31), got nnz={nnz}, B={B}")
+        if self.variable and module._exact_active():
+            # (the exact backward sorts all `nnz` staged positions: stale ids past the live count would move its chunk edges,
+            #  and with them the summation order -- results would no longer be those of the eager call, bit for bit)
+            raise RuntimeError(
+                f"capture(nnz={self.nnz}, B={self.B}, variable=True) is not served in exact mode (OptimType.EXACT_SGD / "
+                "deterministic): the exact kernels take no device id count, so a call shorter than the capacity would not "
+                "reproduce the eager call bit for bit.  Use variable=False, or a module outside exact mode.")
         dev = module.tt_cores[0].device
         self.indices = torch.zeros(self.nnz, dtype=torch.int64, device=dev)
-        self.offsets = (torch.arange(self.B + 1, dtype=torch.int64, device=dev) if offsets is None
-                        else offsets.to(dev, torch.int64).contiguous().clone())
+        if self.variable:   # staged per call (ttemb_stage_call); until the first one: a call without ids
+            self.offsets = torch.zeros(self.B + 1, dtype=torch.int64, device=dev)
+            self.nnz_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            self.offsets = (torch.arange(self.B + 1, dtype=torch.int64, device=dev) if offsets is None
+                            else offsets.to(dev, torch.int64).contiguous().clone())
+            self.nnz_dev = None
         self.output = torch.empty((self.B, module.embedding_dim), dtype=torch.float32, device=dev)
         self.d_output = torch.zeros_like(self.output)
         self._lean = _nat.LeanCalls(module._shape, _nat.Workspace())   # private workspace: pinned for the graphs' lifetime
@@ -645,12 +691,14 @@ class CapturedLookup:
                                     self._lean.ws, opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps,
                                     adam=None if adam is None else (_nat.core_ptrs(adam[0]), adam[1], adam[2]))
         else:
+            # (variable: the route is chosen from the capacities, on the host; the kernels read the live count from nnz_dev)
             def fwd():
-                self.plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output)
+                self.plan = self._lean.forward(cores, self.indices, self.offsets, self.nnz, self.B, self.output,
+                                               nnz_dev=self.nnz_dev)
 
             def bwd():
                 self._lean.backward(cores, state, self.indices, self.offsets, self.nnz, self.B, self.d_output, lr, eps, self.plan,
-                                    adam)
+                                    adam, nnz_dev=self.nnz_dev)
         # Capturing EXECUTES one backward on a zero gradient.  For SGD / Adagrad that leaves everything as it is; an Adam step
         # on g = 0 advances t, decays m and v and, with weight decay, moves the cores: all of it is put back after the
         # capture, so that a captured module equals an eager one step for step.
@@ -698,12 +746,32 @@ class CapturedLookup:
         if self._pointers() != self._baked:
             raise RuntimeError("tt_cores / optimizer_state were re-allocated after capture() (.to(), .data = ..., "
                                "load_state_dict into new storage): capture() again")
+        if self.variable:
+            return self._call_variable(indices, offsets)
         if m.use_cache:   # warm-up: the LFU statistics of a captured step count like those of an eager one
             m.update_cache(indices)
         self.indices.copy_(indices)
         if offsets is not None:
             self.offsets.copy_(offsets)
         return _ReplayLookup.apply(m._cores()[0], self)
+
+    def _call_variable(self, indices: torch.Tensor, offsets: Optional[torch.Tensor]) -> torch.Tensor:
+        m = self.module
+        n = indices.numel()
+        B_live = n if offsets is None else offsets.numel() - 1
+        # every size check before anything is launched
+        if n > self.nnz:
+            raise ValueError(f"{n} ids exceed the captured capacity nnz={self.nnz}: capture() again with a larger one")
+        if B_live > self.B:
+            raise ValueError(f"{B_live} bags exceed the captured capacity B={self.B}"
+                             + (" (a call without offsets is one bag per id)" if offsets is None else "")
+                             + ": capture() again with a larger one")
+        if B_live < 0:
+            raise ValueError("offsets must hold B + 1 entries (include_last_offset): got an empty tensor")
+        if m.use_cache:   # warm-up: the LFU statistics of a captured step count like those of an eager one
+            m.update_cache(indices if indices.dtype == torch.int64 else indices.long())
+        _nat.stage_call(indices, offsets, self.indices, self.offsets, self.nnz_dev)
+        return _ReplayVariableLookup.apply(m._cores()[0], self, n, B_live)
 
 
 # --------------------------------------------------------------------------------------
@@ -910,9 +978,10 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                                 self.cache_state, self.cache_weight.data, self._ws)
             self.warmup = False
 
-    def capture(self, nnz: int, B: int, offsets: Optional[torch.Tensor] = None) -> CapturedLookup:
-        """Fixed-size lookup whose forward and backward replay captured HIP graphs (see ``CapturedLookup``)."""
-        return CapturedLookup(self, nnz, B, offsets)
+    def capture(self, nnz: int, B: int, offsets: Optional[torch.Tensor] = None, *, variable: bool = False) -> CapturedLookup:
+        """Lookup whose forward and backward replay captured HIP graphs (see ``CapturedLookup``): of exactly ``nnz`` ids in
+        ``B`` bags, or, with ``variable=True``, of any size up to those capacities."""
+        return CapturedLookup(self, nnz, B, offsets, variable)
 
     # ---- lookup -------------------------------------------------------------------
     def _cores(self) -> tuple:

@@ -905,6 +905,30 @@ static int backward_into(const Route& r, const DevShape& ds, const CorePtrs& cp,
   return check_hip(hipGetLastError(), "split_pair_kernel");
 }
 
+// ttemb_stage_call: one call of any size into the static buffers of a captured lookup.  Element i of the grid-stride loop is
+// id i (widened from int32 when the caller's are) and offsets word i: the caller's, 0 .. B_live without offsets, n_live for
+// every bag past the live ones.  indices_out past n_live is not touched.  No LDS; 8-byte stores, 512 contiguous bytes a wave.
+__global__ __launch_bounds__(256) void stage_call_kernel(const void* __restrict__ indices_in, int ids_i32, long long n_live,
+                                                         const void* __restrict__ offsets_in, int offs_i32, long long B_live,
+                                                         int64_t* __restrict__ indices_out, int64_t* __restrict__ offsets_out,
+                                                         long long B_cap, int32_t* __restrict__ nnz_dev_out) {
+  const long long total = n_live > B_cap + 1 ? n_live : B_cap + 1;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (first == 0) *nnz_dev_out = (int32_t)n_live;
+  for (long long i = first; i < total; i += stride) {
+    if (i < n_live)
+      indices_out[i] = ids_i32 ? (int64_t) reinterpret_cast<const int32_t*>(indices_in)[i] : reinterpret_cast<const int64_t*>(indices_in)[i];
+    if (i <= B_cap) {
+      int64_t o = n_live;
+      if (i <= B_live)
+        o = offsets_in == nullptr ? (int64_t)i
+                                  : (offs_i32 ? (int64_t) reinterpret_cast<const int32_t*>(offsets_in)[i] : reinterpret_cast<const int64_t*>(offsets_in)[i]);
+      offsets_out[i] = o;
+    }
+  }
+}
+
 }  // namespace ttemb
 
 using namespace ttemb;
@@ -1386,6 +1410,30 @@ int ttemb_backward_adam_window(const ttemb_shape_t* shape, float* const* cores, 
   if (rc) return rc;
   return backward_window(shape, cores, exp_avg, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, hp->lr, hp->eps, workspace,
                          workspace_bytes, stream, &adam, exp_avg_sq);
+}
+
+int ttemb_stage_call(const void* indices_in, int32_t indices_are_i32, int64_t n_live, const void* offsets_in, int32_t offsets_are_i32,
+                     int64_t B_live, int64_t* indices_out, int64_t nnz_cap, int64_t* offsets_out, int64_t B_cap, int32_t* nnz_dev_out,
+                     void* stream) {
+  ApiRange api_range("ttemb_stage_call");
+  if (n_live < 0 || B_live < 0 || nnz_cap < 0 || B_cap < 0) return fail(TTEMB_E_BADARG, "ttemb_stage_call: negative size");
+  if (n_live > nnz_cap)
+    return fail(TTEMB_E_BADARG, "ttemb_stage_call: %lld ids exceed the capacity of %lld", (long long)n_live, (long long)nnz_cap);
+  if (B_live > B_cap)
+    return fail(TTEMB_E_BADARG, "ttemb_stage_call: %lld bags exceed the capacity of %lld", (long long)B_live, (long long)B_cap);
+  if (nnz_cap > 0x7fffffffll) return fail(TTEMB_E_BADARG, "ttemb_stage_call: the id capacity exceeds int32 range (the count word is int32)");
+  if (offsets_in == nullptr && B_live != n_live)
+    return fail(TTEMB_E_BADARG, "ttemb_stage_call: without offsets every id is a bag of its own, but %lld ids came with %lld bags",
+                (long long)n_live, (long long)B_live);
+  if (offsets_out == nullptr || nnz_dev_out == nullptr || (n_live > 0 && (indices_in == nullptr || indices_out == nullptr)))
+    return fail(TTEMB_E_BADARG, "ttemb_stage_call: null buffer");
+  const int64_t total = n_live > B_cap + 1 ? n_live : B_cap + 1;
+  int64_t blocks = (total + 255) / 256;
+  blocks = blocks > 2048 ? 2048 : blocks;   // (memory-bound: the grid is capped, the loop strides over the rest)
+  hipLaunchKernelGGL(stage_call_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), indices_in,
+                     indices_are_i32 != 0 ? 1 : 0, (long long)n_live, offsets_in, offsets_are_i32 != 0 ? 1 : 0, (long long)B_live, indices_out,
+                     offsets_out, (long long)B_cap, nnz_dev_out);
+  return check_hip(hipGetLastError(), "stage_call_kernel");
 }
 
 int ttemb_adam_step(float* weights, float* exp_avg, float* exp_avg_sq, int32_t* step, const float* grads, int64_t n,

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_drop_padding_workspace_bytes", "ttemb_drop_padding", "ttemb_pad_weights",
     "ttemb_backward_adam", "ttemb_backward_adam_window", "ttemb_backward_adam_exact", "ttemb_adam_step",
     "ttemb_bag_max_workspace_bytes", "ttemb_bag_max", "ttemb_bag_max_backward",
+    "ttemb_stage_call",
 )
 
 
@@ -159,6 +160,7 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_drop_padding_workspace_bytes.argtypes = [i64, i64]
     lib.ttemb_drop_padding.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]
     lib.ttemb_pad_weights.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp]
+    lib.ttemb_stage_call.argtypes = [vp, i32, i64, vp, i32, i64, vp, i64, vp, i64, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
@@ -816,6 +818,33 @@ def cache_backward_rowwise_adagrad(cache_loc, rowidx, start: int, start_dev, nnz
                                                         _stream(d_output)))
 
 
+_ID_DTYPES = (torch.int64, torch.int32)
+
+
+def stage_call(indices: torch.Tensor, offsets: Optional[torch.Tensor], indices_out: torch.Tensor, offsets_out: torch.Tensor,
+               nnz_dev_out: torch.Tensor, B_live: Optional[int] = None) -> None:
+    """One call of any size into the static buffers of a captured lookup, in ONE launch (``ttemb_stage_call``): the ids
+    (int64 or int32, widened) into ``indices_out[:n]`` -- the rest of it is not touched --, the offsets (int64 or int32;
+    ``None``: bags of one id) into ``offsets_out[:B_live + 1]``, ``n`` into every offsets word past them and into the int32
+    word ``nnz_dev_out``.  The capacities are the lengths of the two outputs; a call past them raises ``RuntimeError`` with
+    nothing launched."""
+    n = indices.numel()
+    if B_live is None:
+        B_live = n if offsets is None else offsets.numel() - 1
+    if (indices.dtype not in _ID_DTYPES or (offsets is not None and offsets.dtype not in _ID_DTYPES)
+            or indices_out.dtype != torch.int64 or offsets_out.dtype != torch.int64 or nnz_dev_out.dtype != torch.int32):
+        raise ValueError("stage_call: ids and offsets must be int64 or int32, the staged buffers int64 and the count word int32")
+    if offsets_out.numel() < 1 or nnz_dev_out.numel() < 1 or (offsets is not None and B_live > offsets.numel() - 1):
+        raise ValueError("stage_call: offsets_out needs B_cap + 1 entries, nnz_dev_out one int32 and offsets B_live + 1 entries")
+    with _on_device(offsets_out.device):
+        rc = LIB.ttemb_stage_call(_ptr(indices), 1 if indices.dtype == torch.int32 else 0, n, _ptr(offsets),
+                                  1 if offsets is not None and offsets.dtype == torch.int32 else 0, B_live, _ptr(indices_out),
+                                  indices_out.numel(), _ptr(offsets_out), offsets_out.numel() - 1, _ptr(nnz_dev_out),
+                                  _stream(offsets_out))
+    if rc:
+        _check(rc)
+
+
 def core_ptrs(tt_cores: Sequence[torch.Tensor], table: int = 0):
     """Pointer array of the per-table [p_t, row] slices of [num_tables, p_t, row] parameters: what core_views gives,
     without creating view tensors (this sits on the host path of every step)."""
@@ -877,8 +906,9 @@ class LeanCalls:
             key = k
         return key, arr
 
-    def forward(self, cores, indices, offsets, nnz: int, B: int, out, keep_plan: bool = True):
-        """``keep_plan=False``: a forward whose backward never comes (inference): the plan lives and dies in the workspace."""
+    def forward(self, cores, indices, offsets, nnz: int, B: int, out, keep_plan: bool = True, nnz_dev=None):
+        """``keep_plan=False``: a forward whose backward never comes (inference): the plan lives and dies in the workspace.
+        ``nnz_dev`` (int32[1] on the device): the live id count, <= ``nnz``; the launches are sized by ``nnz``."""
         fwd_ws, _, plan_n = self._entry(nnz, B)
         self.core_key, self.core_arr = self._ptrs(cores, self.core_key, self.core_arr)
         dev = out.device
@@ -886,7 +916,8 @@ class LeanCalls:
         plan = torch.empty(plan_n, dtype=torch.uint8, device=dev) if plan_n > 0 and keep_plan else None
         with _on_device(dev):
             rc = LIB.ttemb_forward(self.shape_ref, self.core_arr, indices.data_ptr() if nnz else None, None, offsets.data_ptr(),
-                                   nnz, None, B, out.data_ptr() if B else None, w.data_ptr(), w.numel(),
+                                   nnz, None if nnz_dev is None else nnz_dev.data_ptr(), B, out.data_ptr() if B else None,
+                                   w.data_ptr(), w.numel(),
                                    plan.data_ptr() if plan is not None else None, plan_n if plan is not None else 0, _stream(out))
         if rc:
             _check(rc)
@@ -937,27 +968,30 @@ class LeanCalls:
             g = self.grouped[(nnz, B)] = nnz > 0 and (kernel_family(self.shape, nnz, B, True) & 7) in (FAMILY_GROUPED, FAMILY_GROUPED_WIDE)
         return g
 
-    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan, adam=None):
-        """``adam = (exp_avg_sq, step, AdamParams)``: the fused Adam step, ``state`` then the first moment."""
+    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan, adam=None,
+                 nnz_dev=None):
+        """``adam = (exp_avg_sq, step, AdamParams)``: the fused Adam step, ``state`` then the first moment.  ``nnz_dev``: as
+        in ``forward``."""
         _, bwd_ws, plan_n = self._entry(nnz, B)
         self.core_key, self.core_arr = self._ptrs(cores, self.core_key, self.core_arr)
         dev = d_output.device
         w = self.ws.get(bwd_ws, dev)
         pp, pn = (plan.data_ptr(), plan_n) if plan is not None else (None, 0)
         ids = indices.data_ptr() if nnz else None
+        cnt = None if nnz_dev is None else nnz_dev.data_ptr()
         with _on_device(dev):
             if adam is not None:
                 self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
                 self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
                 rc = LIB.ttemb_backward_adam(self.shape_ref, self.core_arr, self.state_arr, self.state2_arr, adam[1].data_ptr(), ids,
-                                             None, offsets.data_ptr(), nnz, None, B, d_output.data_ptr() if B else None,
+                                             None, offsets.data_ptr(), nnz, cnt, B, d_output.data_ptr() if B else None,
                                              ctypes.byref(adam[2]), w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
             elif state is None:
-                rc = LIB.ttemb_backward_sgd(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, None, B,
+                rc = LIB.ttemb_backward_sgd(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, cnt, B,
                                             d_output.data_ptr() if B else None, lr, w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
             else:
                 self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
-                rc = LIB.ttemb_backward_adagrad(self.shape_ref, self.core_arr, self.state_arr, ids, None, offsets.data_ptr(), nnz, None,
+                rc = LIB.ttemb_backward_adagrad(self.shape_ref, self.core_arr, self.state_arr, ids, None, offsets.data_ptr(), nnz, cnt,
                                                 B, d_output.data_ptr() if B else None, lr, eps, w.data_ptr(), w.numel(), pp, pn,
                                                 _stream(d_output))
         if rc:

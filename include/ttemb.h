@@ -298,6 +298,28 @@ int ttemb_backward_adagrad_window(const ttemb_shape_t* shape, float* const* core
                                   int64_t bag0, int64_t B, const float* d_output, float lr, float eps,
                                   void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Stage one call of ANY size into the static buffers of a captured lookup (no counterpart in the reference: it has no
+ * graph capture).  A graph captured with nnz = nnz_cap, B = B_cap and nnz_dev = nnz_dev_out serves every call of
+ * n_live <= nnz_cap ids in B_live <= B_cap bags once this ran in front of its replay.  ONE launch on `stream`, no host
+ * synchronisation, no workspace.  `indices_in` holds n_live ids, int64 or (indices_are_i32 != 0) int32, widened here;
+ * `offsets_in` the B_live + 1 bag boundaries, int64 or (offsets_are_i32 != 0) int32, or NULL: bags of one id, which needs
+ * B_live == n_live.  Written:
+ *     indices_out[0 : n_live]              the ids
+ *     indices_out[n_live : nnz_cap]        NOT touched (ids that were valid earlier; no kernel reads past the count)
+ *     offsets_out[0 : B_live + 1]          the offsets (0 .. B_live without offsets_in)
+ *     offsets_out[B_live + 1 : B_cap + 1]  n_live: every bag past the live ones is empty
+ *     *nnz_dev_out                         n_live
+ * TTEMB_E_BADARG, with nothing launched, for a negative size, n_live > nnz_cap, B_live > B_cap, n_live or nnz_cap >= 2^31
+ * (the count word is int32), a null output, null ids with n_live > 0, or offsets_in == NULL with B_live != n_live.
+ * n_live == 0 is valid.  The inputs must not overlap the outputs.
+ * ------------------------------------------------------------------------------- */
+int ttemb_stage_call(const void* indices_in, int32_t indices_are_i32, int64_t n_live,
+                     const void* offsets_in /* nullable */, int32_t offsets_are_i32, int64_t B_live,
+                     int64_t* indices_out, int64_t nnz_cap,
+                     int64_t* offsets_out, int64_t B_cap,
+                     int32_t* nnz_dev_out, void* stream);
+
 /* Flat optimiser epilogues over n floats (used after the data-parallel all-reduce of
  * the flattened core gradients; same arithmetic as tt_embeddings_cuda.cu:381-419). */
 int ttemb_sgd_step(float* weights, const float* grads, int64_t n, float lr, void* stream);
