@@ -9,6 +9,12 @@ C ABI in ``include/ttemb.h``) through ``ttemb_native``.  There is no
 never leave the chip), and no host synchronisation in ``forward`` -- the split
 between TT-computed and cached ids stays on the device.
 
+Every call form goes through one front end: ``_prepare`` (the argument checks, in one order for every form, before anything
+is launched; ids and offsets as the kernels read them; the LFU statistics; the exact-mode decision) and ``_route`` (the
+effective mode, ``padding_idx`` and the weights pick the lookup and the pooling around it).  Several tables are either
+windows the kernels read on the device or one host split (``_each_table``); dense gradients of every autograd bridge are
+delivered by ``_deliver_dense``.
+
 No CPU fallback exists: modules can be *constructed* without a GPU (so that shape
 logic, initialisers and checkpoints can be exercised anywhere) but ``forward`` on
 CPU tensors raises ``RuntimeError``.
@@ -216,6 +222,54 @@ def suggested_tt_shapes(n: int, d: int = 3, allow_round_up: bool = True) -> List
 # --------------------------------------------------------------------------------------
 # autograd bridge
 # --------------------------------------------------------------------------------------
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    """The incoming gradient as the kernels read it: contiguous float32."""
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.contiguous().float()
+    return t
+
+
+def _aligned(t: torch.Tensor) -> torch.Tensor:
+    """``_f32`` at a 16-byte address: what the bag kernels' float4 accesses need (a gradient can arrive as a view)."""
+    t = _f32(t)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _deliver_dense(m: "TableBatchedTTEmbeddingBag", table: int, use_bucket: bool, run, into_grad: bool = False):
+    """Dense core gradients of one table, for every bridge: ``run(dst)`` is the native backward writing one [p, row]
+    gradient per core into the tensors ``dst``.  A data-parallel wrapper may have provided one flat bucket for them
+    (``ttemb_dist``, ``_dense_grad_out``); where the bridge may use it (``use_bucket``) they are produced straight into it and
+    nothing is handed to autograd (no AccumulateGrad, no views): returns None.  Else returns one gradient per
+    [num_tables, p, row] parameter -- or, ``into_grad`` (a bridge without the cores among its inputs), adds them to ``.grad``."""
+    bucket = m._dense_grad_out
+    if bucket is not None and use_bucket:
+        if m._bucket_filled:
+            # a second backward before dp.step() (micro-batches, two lookups through one module): the kernels overwrite
+            # their destination, so this one goes to scratch and is added -- what AccumulateGrad does
+            more = [torch.empty_like(b) for b in bucket]
+            run(more)
+            torch._foreach_add_(bucket, more)
+        else:
+            run(bucket)
+            m._bucket_filled = True
+        return None
+    # (a bucket the bridge may not fill on its own -- a live cache, whose cache_weight gradient goes through autograd --
+    #  still receives the gradients: autograd then hands the wrapper views of it)
+    grads = bucket or [torch.empty_like(c[table]) for c in m.tt_cores]
+    run(grads)
+    if m.num_tables == 1:
+        full = [g.unsqueeze(0) for g in grads]
+    else:  # only this table's slice of the [num_tables, p, row] parameter gets gradient
+        full = [torch.zeros_like(c.data) for c in m.tt_cores]
+        for z, g in zip(full, grads):
+            z[table] = g
+    if into_grad:
+        for c, g in zip(m.tt_cores, full):
+            c.grad = g if c.grad is None else c.grad + g
+        return None
+    return full
+
+
 class TTLookupFunction(torch.autograd.Function):
     """forward = TT rows (+ cached rows) bag-summed; backward = fused optimiser step
     (``sparse``) or dense core gradients.  Reference: tt_embeddings_ops.py:130-366."""
@@ -255,73 +309,41 @@ class TTLookupFunction(torch.autograd.Function):
         m, table, B = ctx.module, ctx.table, ctx.B
         indices, rowidx, nnz_dev, cache_loc, offsets = ctx.inputs
         nnz = indices.numel()
-        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
-            d_output = d_output.contiguous().float()
+        d_output = _f32(d_output)
         cores = _nat.core_ptrs(m.tt_cores, table)
         n_fixed = 9
+        cached = ctx.live_cache and nnz > 0
         if m.sparse:
-            if m.optimizer in _SGD_LIKE:
-                _nat.backward_sgd(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output,
-                                  float(m.learning_rate), m._ws, ctx.plan, offsets)
-                if ctx.live_cache and nnz > 0:
-                    _nat.cache_backward_sgd(cache_loc, rowidx, 0, nnz_dev, nnz, d_output,
-                                            float(m.learning_rate), m.cache_weight.data,
-                                            nnz_dev[1:] if nnz_dev.numel() > 1 else None)
-            elif m.optimizer == OptimType.ADAM:   # (never with a live cache: the constructor refuses that combination)
-                state, adam = _step_call(m, table)
+            state, adam = _step_call(m, table)
+            lr, eps = float(m.learning_rate), float(m.eps)
+            if adam is not None:   # (never with a live cache: the constructor refuses that combination)
                 _nat.backward_adam(m._shape, cores, state, adam[0], adam[1], indices, rowidx, nnz, nnz_dev, B, d_output,
                                    adam[2], m._ws, ctx.plan, offsets)
+            elif state is None:
+                _nat.backward_sgd(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, m._ws, ctx.plan, offsets)
+                if cached:
+                    _nat.cache_backward_sgd(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, lr, m.cache_weight.data,
+                                            nnz_dev[1:] if nnz_dev.numel() > 1 else None)
             else:
-                state = _nat.core_ptrs(list(m.optimizer_state), table)
-                _nat.backward_adagrad(m._shape, cores, state, indices, rowidx, nnz, nnz_dev, B, d_output,
-                                      float(m.learning_rate), float(m.eps), m._ws, ctx.plan, offsets)
-                if ctx.live_cache and nnz > 0:
-                    _nat.cache_backward_rowwise_adagrad(cache_loc, rowidx, 0, nnz_dev, nnz, d_output,
-                                                        float(m.learning_rate), float(m.eps),
+                _nat.backward_adagrad(m._shape, cores, state, indices, rowidx, nnz, nnz_dev, B, d_output, lr, eps, m._ws,
+                                      ctx.plan, offsets)
+                if cached:
+                    _nat.cache_backward_rowwise_adagrad(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, lr, eps,
                                                         m.cache_optimizer_state, m.cache_weight.data)
             return (None,) * (n_fixed + len(m.tt_cores))
-        # a data-parallel wrapper may have provided one flat bucket for the gradients (ttemb_dist): they are then
-        # produced straight into it and nothing is handed back to autograd (no AccumulateGrad, no views)
-        bucket = getattr(m, "_dense_grad_out", None)
         # (for ttemb_dist: did this gradient come from a grouped backward -- the family with bounded device-side waits,
         #  whose last kernel leaves its verdict in the workspace header?  Host-side rule, launches nothing.)
-        fam_key = (nnz, B, rowidx is None, _nat.path_epoch)
-        grouped = m._family_cache.get(fam_key)
-        if grouped is None:
-            if len(m._family_cache) > 256:
-                m._family_cache.clear()
-            grouped = m._family_cache[fam_key] = nnz > 0 and (_nat.kernel_family(m._shape, nnz, B, rowidx is None) & 7) in (
-                _nat.FAMILY_GROUPED, _nat.FAMILY_GROUPED_WIDE)
-        m._last_bwd_grouped = grouped
-        if bucket is not None and not ctx.live_cache:
-            if m._bucket_filled:
-                # a second backward before dp.step() (micro-batches, two lookups through one module): the kernels
-                # overwrite their destination, so this one goes to scratch and is added -- what AccumulateGrad does
-                more = [torch.empty_like(b) for b in bucket]
-                _nat.backward_dense(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, more, m._ws,
-                                    ctx.plan, offsets)
-                torch._foreach_add_(bucket, more)
-            else:
-                _nat.backward_dense(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, bucket, m._ws,
-                                    ctx.plan, offsets)
-                m._bucket_filled = True
+        m._last_bwd_grouped = _nat.is_grouped(m._shape, nnz, B, rowidx is None)
+        full = _deliver_dense(m, table, m.num_tables == 1 and not ctx.live_cache,
+                              lambda dst: _nat.backward_dense(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, dst,
+                                                              m._ws, ctx.plan, offsets))
+        if full is None:
             return (None,) * (n_fixed + len(m.tt_cores))
-        grads = bucket or [torch.empty_like(c[table] if c.dim() == 3 else c) for c in m.tt_cores]
-        _nat.backward_dense(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, grads, m._ws, ctx.plan,
-                            offsets)
         d_cache = None
         if ctx.live_cache:
             d_cache = torch.empty_like(m.cache_weight.data)
             _nat.cache_backward_dense(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, d_cache,
                                       nnz_dev[1:] if nnz_dev.numel() > 1 else None)
-        full = []
-        for t, g in enumerate(grads):
-            if m.num_tables == 1:
-                full.append(g.unsqueeze(0))
-            else:  # only this table's slice of the [num_tables, p, row] parameter gets gradient
-                z = torch.zeros_like(m.tt_cores[t].data)
-                z[table] = g
-                full.append(z)
         return (None,) * (n_fixed - 1) + (d_cache,) + tuple(full)
 
 
@@ -347,8 +369,7 @@ class _TablesLookup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         m, B, indices, offsets = ctx.module, ctx.B, ctx.indices, ctx.offsets
-        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
-            d_output = d_output.contiguous().float()
+        d_output = _f32(d_output)
         T = m.num_tables
         if m.sparse:
             for k in range(T):
@@ -381,8 +402,7 @@ class _SparseLookup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         m = ctx.module
-        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
-            d_output = d_output.contiguous().float()
+        d_output = _f32(d_output)
         state = None if m.optimizer in _SGD_LIKE else m._states()
         m._lean.backward(m._cores(), state, ctx.indices, ctx.offsets, ctx.indices.numel(), ctx.B, d_output,
                          float(m.learning_rate), float(m.eps), ctx.plan, m._adam_lean())
@@ -412,22 +432,12 @@ class _BucketLookup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         m = ctx.module
-        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
-            d_output = d_output.contiguous().float()
-        bucket = m._dense_grad_out
+        d_output = _f32(d_output)
         nnz = ctx.indices.numel()
-        if bucket is None:   # the wrapper was detached between forward and backward: gradients through .grad
-            grads = [torch.empty_like(c[0]) for c in m.tt_cores]
-            m._last_bwd_grouped = m._lean.backward_dense(m._cores(), ctx.indices, ctx.offsets, nnz, ctx.B, d_output, grads, ctx.plan)
-            for c, g in zip(m.tt_cores, grads):
-                c.grad = g.unsqueeze(0) if c.grad is None else c.grad + g.unsqueeze(0)
-        elif m._bucket_filled:   # a second backward before dp.step(): through scratch, added (what AccumulateGrad does)
-            more = [torch.empty_like(b) for b in bucket]
-            m._last_bwd_grouped = m._lean.backward_dense(m._cores(), ctx.indices, ctx.offsets, nnz, ctx.B, d_output, more, ctx.plan)
-            torch._foreach_add_(bucket, more)
-        else:
-            m._last_bwd_grouped = m._lean.backward_dense(m._cores(), ctx.indices, ctx.offsets, nnz, ctx.B, d_output, bucket, ctx.plan)
-            m._bucket_filled = True
+        m._last_bwd_grouped = _nat.is_grouped(m._shape, nnz, ctx.B)
+        # (no bucket: the wrapper was detached between forward and backward -- the gradients then go through .grad)
+        _deliver_dense(m, 0, True, lambda dst: m._lean.backward_dense(m._cores(), ctx.indices, ctx.offsets, nnz, ctx.B,
+                                                                      d_output, dst, ctx.plan), into_grad=True)
         return None, None, None, None, None
 
 
@@ -452,8 +462,7 @@ class _ExactLookup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
         m, table, B, indices, offsets = ctx.module, ctx.table, ctx.B, ctx.indices, ctx.offsets
-        if d_output.dtype != torch.float32 or not d_output.is_contiguous():
-            d_output = d_output.contiguous().float()
+        d_output = _f32(d_output)
         cores = _nat.core_ptrs(m.tt_cores, table)
         n_fixed = 5
         if m.sparse:
@@ -462,34 +471,9 @@ class _ExactLookup(torch.autograd.Function):
                                 lr=float(m.learning_rate), eps=float(m.eps), adam=adam)
             return (None,) * (n_fixed + len(m.tt_cores))
         m._last_bwd_grouped = False   # no bounded device-side waits: nothing in the workspace header to look at
-        bucket = getattr(m, "_dense_grad_out", None)
-        if bucket is not None and m.num_tables == 1:
-            if m._bucket_filled:   # a second backward before dp.step(): to scratch, then added (what AccumulateGrad does)
-                more = [torch.empty_like(b) for b in bucket]
-                _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=more)
-                torch._foreach_add_(bucket, more)
-            else:
-                _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=bucket)
-                m._bucket_filled = True
-            return (None,) * (n_fixed + len(m.tt_cores))
-        grads = [torch.empty_like(c[table] if c.dim() == 3 else c) for c in m.tt_cores]
-        _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=grads)
-        full = []
-        for t, g in enumerate(grads):
-            if m.num_tables == 1:
-                full.append(g.unsqueeze(0))
-            else:  # only this table's slice of the [num_tables, p, row] parameter gets gradient
-                z = torch.zeros_like(m.tt_cores[t].data)
-                z[table] = g
-                full.append(z)
-        return (None,) * n_fixed + tuple(full)
-
-
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    """Contiguous float32 at a 16-byte address: what the bag kernels' float4 accesses need (a gradient can arrive as a view)."""
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        t = t.contiguous().float()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
+        full = _deliver_dense(m, table, m.num_tables == 1,
+                              lambda dst: _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, d_cores=dst))
+        return (None,) * n_fixed + (tuple(full) if full is not None else (None,) * len(m.tt_cores))
 
 
 class _WeightedBag(torch.autograd.Function):
@@ -588,40 +572,24 @@ class _PadWeights(torch.autograd.Function):
 
 
 class _ReplayLookup(torch.autograd.Function):
-    """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each."""
+    """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each.  ``n_live`` / ``B_live``: None
+    for a fixed capture; the ids and bags of a ``capture(..., variable=True)`` call, already staged -- the forward then hands
+    out the live rows of the static output and the backward fills the live rows of the static gradient (the rows past them
+    belong to empty bags, which no kernel reads) and replays, unless the call had no id."""
 
     @staticmethod
-    def forward(ctx, anchor: torch.Tensor, cap: "CapturedLookup") -> torch.Tensor:
-        ctx.cap = cap
-        cap.fwd_graph.replay()
-        return cap.output
-
-    @staticmethod
-    def backward(ctx, d_output: torch.Tensor):
-        cap = ctx.cap
-        cap.d_output.copy_(d_output)
-        cap.bwd_graph.replay()
-        return None, None
-
-
-class _ReplayVariableLookup(torch.autograd.Function):
-    """Autograd node of a ``capture(..., variable=True)`` call of ``n_live`` ids in ``B_live`` bags, already staged: the
-    forward replays and hands out the live rows of the static output; the backward fills the live rows of the static
-    gradient -- the rows past them belong to empty bags, which no kernel reads -- and replays, unless the call had no id."""
-
-    @staticmethod
-    def forward(ctx, anchor: torch.Tensor, cap: "CapturedLookup", n_live: int, B_live: int) -> torch.Tensor:
+    def forward(ctx, anchor: torch.Tensor, cap: "CapturedLookup", n_live: Optional[int] = None,
+                B_live: Optional[int] = None) -> torch.Tensor:
         ctx.cap, ctx.n_live, ctx.B_live = cap, n_live, B_live
         cap.fwd_graph.replay()
-        return cap.output[:B_live]
+        return cap.output if B_live is None else cap.output[:B_live]
 
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
-        if ctx.n_live == 0:   # a call without ids is a no-op for every optimiser and does not advance Adam's t (include/ttemb.h)
-            return None, None, None, None
         cap = ctx.cap
-        cap.d_output[:ctx.B_live].copy_(d_output)
-        cap.bwd_graph.replay()
+        if ctx.n_live != 0:   # a call without ids is a no-op for every optimiser and does not advance Adam's t (include/ttemb.h)
+            (cap.d_output if ctx.B_live is None else cap.d_output[:ctx.B_live]).copy_(d_output)
+            cap.bwd_graph.replay()
         return None, None, None, None
 
 
@@ -753,7 +721,7 @@ class CapturedLookup:
         self.indices.copy_(indices)
         if offsets is not None:
             self.offsets.copy_(offsets)
-        return _ReplayLookup.apply(m._cores()[0], self)
+        return _ReplayLookup.apply(m._cores()[0], self, None, None)
 
     def _call_variable(self, indices: torch.Tensor, offsets: Optional[torch.Tensor]) -> torch.Tensor:
         m = self.module
@@ -771,7 +739,7 @@ class CapturedLookup:
         if m.use_cache:   # warm-up: the LFU statistics of a captured step count like those of an eager one
             m.update_cache(indices if indices.dtype == torch.int64 else indices.long())
         _nat.stage_call(indices, offsets, self.indices, self.offsets, self.nnz_dev)
-        return _ReplayVariableLookup.apply(m._cores()[0], self, n, B_live)
+        return _ReplayLookup.apply(m._cores()[0], self, n, B_live)
 
 
 # --------------------------------------------------------------------------------------
@@ -914,7 +882,6 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         self._pad_partition = True    # padding_idx: drop the pad ids where the grouped kernels serve (False: masked rows only)
         self._last_pad_route: Optional[str] = None   # route of the last padded call ("partition" / "masked")
         self._bucket_filled = False   # set by the backward when it wrote the core gradients into the wrapper's bucket
-        self._family_cache: dict = {}  # (nnz, B, ...) -> "the backward of this size runs on the grouped kernels" (ttemb_dist)
         self._shape = _nat.make_shape(self.tt_p_shapes, self.tt_q_shapes, self.tt_ranks)
         self._ws = _nat.Workspace()
         self._lean = _nat.LeanCalls(self._shape, self._ws)
@@ -1054,11 +1021,11 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             return False
         raise RuntimeError(f"TTEmbeddingBag: exact mode was requested but is unavailable: {reason}")
 
-    def _lookup_one_table(self, table: int, B: int, indices: torch.Tensor, offsets: torch.Tensor,
-                          exact: Optional[bool] = None) -> torch.Tensor:
+    def _lookup_one_table(self, table: int, B: int, indices: torch.Tensor, offsets: torch.Tensor, exact: bool) -> torch.Tensor:
+        """[B, D] bag sums of one table through the autograd bridge that serves the call."""
         nnz = indices.numel()
         dev = indices.device
-        if exact if exact is not None else self._exact_active():
+        if exact:
             return _ExactLookup.apply(self, table, B, indices, offsets, *self.tt_cores)
         live = self.use_cache and not self.warmup
         if not live:  # rows are derived from `offsets` inside the native calls: no separate launch, no tensor
@@ -1086,7 +1053,7 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         stamp = getattr(self, "_dup_stamp", None)
         if stamp is None or stamp.device != dev or stamp.numel() != self.cache_weight.shape[0]:
             stamp = self._dup_stamp = torch.empty(self.cache_weight.shape[0], dtype=torch.int32, device=dev)
-        # the LFU update of this batch rides in the probe pass (forward() skipped update_cache for it)
+        # the LFU update of this batch rides in the probe pass (_prepare() skipped update_cache for it)
         freq = self.cache_freq if self._fused_probe() else None
         _nat.preprocess(indices, offsets, B, False, self.hashtbl, self.cache_state, part, rowidx, loc, nnz_tt,
                         self._ws, stamp, 0, freq)
@@ -1108,41 +1075,47 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         rows = self._lookup_one_table(table, nnz, indices, self._bags_of_one(nnz, indices.device), exact)
         return _WeightedBag.apply(rows, weights, offsets, self)
 
-    def _pooled(self, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
-                tables_dim: bool) -> torch.Tensor:
-        """``forward`` with ``per_sample_weights`` or in ``mode="mean"``; ``tables_dim``: return [num_tables, B, D]."""
-        if not indices.is_cuda:
-            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
-        if weights is not None:
-            if self.mode != "sum":
-                raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
-                                 "(as in torch.nn.functional.embedding_bag)")
-            _nat._check_weights(weights, indices.numel(), indices)   # before anything is launched
-            weights = weights.contiguous()
-        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
-        assert (offsets.numel() - 1) % self.num_tables == 0
-        T, B = self.num_tables, (offsets.numel() - 1) // self.num_tables
-        if not self._fused_probe():
-            self.update_cache(indices)
-        exact = self._exact_active()
-        if weights is None:   # mean: today's bag sums (no host synchronisation wherever the lookup has none), then / len
-            sums = (self._lookup_one_table(0, B, indices, offsets, exact) if T == 1
-                    else self._lookup_tables(indices, offsets, B, exact))
-            out = _BagMean.apply(sums, offsets)
-        elif T == 1:
-            out = self._weighted_one_table(0, indices, offsets, weights, exact)
-        elif B == 0:
-            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=indices.device)
-        else:
-            # several tables with weights: the id list is split on the host (one synchronisation), one call per table
-            bounds = offsets[:: B].tolist()
-            outs = []
-            for k in range(T):
-                lo, hi = int(bounds[k]), int(bounds[k + 1])
-                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
-                outs.append(self._weighted_one_table(k, indices[lo:hi].contiguous(), offs_k, weights[lo:hi], exact))
-            out = torch.stack(outs, 0)
-        return out.unsqueeze(0) if tables_dim and T == 1 else out
+    def _masked_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
+                          mode: str, exact: bool) -> torch.Tensor:
+        """Masked-rows route of a padded call: the bags-of-one rows of every id, pooled with the weights of ``_PadWeights``
+        (0 for a pad id, 1 / len' for a mean)."""
+        w2 = _PadWeights.apply(weights, indices, offsets, self.padding_idx, mode == "mean")
+        return self._weighted_one_table(table, indices, offsets, w2, exact)
+
+    def _pad_route(self, nnz: int, B: int, weighted: bool, exact: bool) -> str:
+        """"partition" (pad ids never reach the TT kernels) where the row-index lookup of this size runs on the grouped
+        kernels; else "masked" (see DESIGN §4.8).  Recorded in ``_last_pad_route``."""
+        masked = (weighted or exact or self.num_tables != 1 or (self.use_cache and not self.warmup) or B == 0
+                  or not self._pad_partition or not _nat.is_grouped(self._shape, nnz, B, False))
+        route = self._last_pad_route = "masked" if masked else "partition"
+        return route
+
+    def _drop_padding(self, indices: torch.Tensor, offsets: torch.Tensor):
+        """Staging of the partition route: (kept ids, their bags, the compacted offsets, the kept count -- which stays on the
+        device: the lookup of the kept ids runs in the row-index form of the live cache)."""
+        dev = indices.device
+        ids, rows = torch.empty_like(indices), torch.empty_like(indices)
+        offs = torch.empty(offsets.numel(), dtype=torch.int64, device=dev)
+        kept = torch.empty(1, dtype=torch.int32, device=dev)
+        _nat.drop_padding(indices, offsets, self.padding_idx, ids, rows, offs, kept, self._ws)
+        return ids, rows, offs, kept
+
+    def _max_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, exact: bool) -> torch.Tensor:
+        """``mode="max"`` on one table.  One row per id (the lookup of bags of one, whichever bridge serves it), then
+        ``_BagMax``.  With ``padding_idx``: where ``_pad_route`` answers "partition", the pad ids are dropped first and only
+        the kept ids are looked up; else every id is looked up and ``_BagMax`` skips the pad positions."""
+        nnz, pad = indices.numel(), self.padding_idx
+        ones = self._bags_of_one(nnz, indices.device)
+        if pad is not None and self._pad_route(nnz, offsets.numel() - 1, False, exact) == "partition":
+            ids, _, offs, kept = self._drop_padding(indices, offsets)   # (the kept ids' bags: not needed, one row per id)
+            # kept id i -> row i of the rows buffer; the rows past the kept count have no writer and no reader (`offs` ends
+            # at the kept count)
+            rows = TTLookupFunction.apply(self, table, nnz, ids, ones[:nnz], ones, kept, None, None, *self.tt_cores)
+            return _BagMax.apply(rows, offs, self, None, 0)
+        rows = self._lookup_one_table(table, nnz, indices, ones, exact)
+        if pad is None:
+            return _BagMax.apply(rows, offsets, self, None, 0)
+        return _BagMax.apply(rows, offsets, self, indices, pad)   # masked route: the pad positions are skipped
 
     def _fixed_bags(self, indices: torch.Tensor, offsets: Optional[torch.Tensor], weights: Optional[torch.Tensor]):
         """2-D ``indices[rows, N]`` without offsets: ``rows`` bags of N ids (for several tables, the num_tables * B bags
@@ -1166,181 +1139,92 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             raise ValueError("offsets is required when indices is 1-D")
         return indices, offsets, weights
 
-    def _masked_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
-                          exact: bool) -> torch.Tensor:
-        """Masked-rows route of a padded call: one row per id (the lookup of bags of one, whichever bridge serves it), then
-        the bag sums with the weights of ``_PadWeights`` (0 for a pad id, 1 / len' for a mean)."""
-        w2 = _PadWeights.apply(weights, indices, offsets, self.padding_idx, self.mode == "mean")
-        nnz = indices.numel()
-        rows = self._lookup_one_table(table, nnz, indices, self._bags_of_one(nnz, indices.device), exact)
-        return _WeightedBag.apply(rows, w2, offsets, self)
-
-    def _pad_route(self, nnz: int, B: int, weighted: bool, exact: bool) -> str:
-        """"partition" (pad ids never reach the TT kernels) where the row-index lookup of this size runs on the grouped
-        kernels; else "masked" (see DESIGN §4.8)."""
-        if (weighted or exact or self.num_tables != 1 or (self.use_cache and not self.warmup) or nnz == 0 or B == 0
-                or not self._pad_partition):
-            return "masked"
-        key = (nnz, B, "pad", _nat.path_epoch)
-        route = self._family_cache.get(key)
-        if route is None:
-            if len(self._family_cache) > 256:
-                self._family_cache.clear()
-            fam = _nat.kernel_family(self._shape, nnz, B, False) & 7
-            route = self._family_cache[key] = ("partition" if fam in (_nat.FAMILY_GROUPED, _nat.FAMILY_GROUPED_WIDE)
-                                               else "masked")
-        return route
-
-    def _padded(self, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor],
-                tables_dim: bool) -> torch.Tensor:
-        """``forward`` with ``padding_idx`` set (1-D ids and their offsets by now)."""
+    def _prepare(self, indices: torch.Tensor, offsets: Optional[torch.Tensor], weights: Optional[torch.Tensor],
+                 mode: Optional[str]):
+        """The prologue of every call: the arguments are checked before anything is launched, then
+        ``(mode, ids, offsets, weights, B, exact)`` -- the effective mode (the per-call one, else the constructor's), 1-D
+        contiguous int64 ids and offsets, flat float32 weights or None, the bags per table, whether exact mode serves the
+        call -- with the LFU statistics of a warming cache updated."""
+        if mode is None:
+            mode = self.mode
+        elif mode not in ("sum", "mean", "max"):
+            raise ValueError(f"mode must be 'sum', 'mean' or 'max', got {mode!r}")
+        if weights is not None and mode == "max":
+            raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
+                             "(as in torch.nn.functional.embedding_bag)")
+        if offsets is None or indices.dim() != 1:
+            indices, offsets, weights = self._fixed_bags(indices, offsets, weights)
         if not indices.is_cuda:
             raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
         if weights is not None:
-            if self.mode != "sum":
+            if mode != "sum":
                 raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
                                  "(as in torch.nn.functional.embedding_bag)")
             _nat._check_weights(weights, indices.numel(), indices)
             weights = weights.contiguous()
-        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
-        assert (offsets.numel() - 1) % self.num_tables == 0
-        T, B, nnz = self.num_tables, (offsets.numel() - 1) // self.num_tables, indices.numel()
-        dev = indices.device
-        if not self._fused_probe():
+        if indices.dtype != torch.int64 or not indices.is_contiguous():
+            indices = indices.long().contiguous()
+        if offsets.dtype != torch.int64 or not offsets.is_contiguous():
+            offsets = offsets.long().contiguous()
+        B = offsets.numel() - 1
+        if self.num_tables != 1:
+            assert B % self.num_tables == 0
+            B //= self.num_tables
+        if self.use_cache and not self._fused_probe():   # (fused: the LFU update rides in the probe pass of the lookup)
             self.update_cache(indices)
-        exact = self._exact_active()
-        route = self._last_pad_route = self._pad_route(nnz, B, weights is not None, exact)
-        if route == "partition":
-            # pad ids never reach the TT kernels: the lookup runs on the kept ids and the compacted bags, the kept count
-            # stays on the device (the row-index form of the live cache)
-            ids = torch.empty_like(indices)
-            rows = torch.empty_like(indices)
-            offs = torch.empty(B + 1, dtype=torch.int64, device=dev)
-            kept = torch.empty(1, dtype=torch.int32, device=dev)
-            _nat.drop_padding(indices, offsets, self.padding_idx, ids, rows, offs, kept, self._ws)
-            out = TTLookupFunction.apply(self, 0, B, ids, rows, offs, kept, None, None, *self.tt_cores)
-            if self.mode == "mean":
-                out = _BagMean.apply(out, offs)
-        elif T == 1:
-            out = self._masked_one_table(0, indices, offsets, weights, exact)
-        elif B == 0:
-            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=dev)
-        else:
-            # several tables: the id list is split on the host (one synchronisation), as for weighted calls
-            bounds = offsets[:: B].tolist()
-            outs = []
-            for k in range(T):
-                lo, hi = int(bounds[k]), int(bounds[k + 1])
-                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
-                outs.append(self._masked_one_table(k, indices[lo:hi].contiguous(), offs_k,
-                                                   None if weights is None else weights[lo:hi], exact))
-            out = torch.stack(outs, 0)
-        return out.unsqueeze(0) if tables_dim and T == 1 else out
+        return mode, indices, offsets, weights, B, self._exact_active()
 
-    def _max_one_table(self, table: int, indices: torch.Tensor, offsets: torch.Tensor, exact: bool) -> torch.Tensor:
-        """``mode="max"`` on one table.  One row per id (the lookup of bags of one, whichever bridge serves it), then
-        ``_BagMax``.  With ``padding_idx``: where ``_pad_route`` answers "partition", the pad ids are dropped first and only
-        the kept ids are looked up (row-index form, the kept count stays on the device); else every id is looked up and
-        ``_BagMax`` skips the pad positions."""
-        nnz, B, dev = indices.numel(), offsets.numel() - 1, indices.device
-        pad = self.padding_idx
-        ones = self._bags_of_one(nnz, dev)
-        if pad is None:
-            return _BagMax.apply(self._lookup_one_table(table, nnz, indices, ones, exact), offsets, self, None, 0)
-        route = self._last_pad_route = self._pad_route(nnz, B, False, exact)
-        if route == "partition":
-            ids = torch.empty_like(indices)
-            bags = torch.empty_like(indices)   # (the bags of the kept ids: not needed, the rows are looked up one per id)
-            offs = torch.empty(B + 1, dtype=torch.int64, device=dev)
-            kept = torch.empty(1, dtype=torch.int32, device=dev)
-            _nat.drop_padding(indices, offsets, pad, ids, bags, offs, kept, self._ws)
-            # kept id i -> row i of the rows buffer; the rows past the kept count have no writer and no reader (`offs` ends
-            # at the kept count)
-            rows = TTLookupFunction.apply(self, table, nnz, ids, ones[:nnz], ones, kept, None, None, *self.tt_cores)
-            return _BagMax.apply(rows, offs, self, None, 0)
-        return _BagMax.apply(self._lookup_one_table(table, nnz, indices, ones, exact), offsets, self, indices, pad)
-
-    def _max_pooled(self, indices: torch.Tensor, offsets: torch.Tensor, tables_dim: bool) -> torch.Tensor:
-        """``forward(..., mode="max")`` (1-D ids and their offsets by now)."""
-        if not indices.is_cuda:
-            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
-        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
-        assert (offsets.numel() - 1) % self.num_tables == 0
-        T, B = self.num_tables, (offsets.numel() - 1) // self.num_tables
-        if not self._fused_probe():
-            self.update_cache(indices)
-        exact = self._exact_active()
-        if T == 1:
-            out = self._max_one_table(0, indices, offsets, exact)
-        elif B == 0:
-            return torch.zeros((T, 0, self.embedding_dim), dtype=torch.float32, device=indices.device)
-        else:
-            # several tables: the id list is split on the host (one synchronisation), as for weighted calls
-            bounds = offsets[:: B].tolist()
-            outs = []
-            for k in range(T):
-                lo, hi = int(bounds[k]), int(bounds[k + 1])
-                offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
-                outs.append(self._max_one_table(k, indices[lo:hi].contiguous(), offs_k, exact))
-            out = torch.stack(outs, 0)
-        return out.unsqueeze(0) if tables_dim and T == 1 else out
-
-    def _per_call_mode(self, mode: str, indices: torch.Tensor, offsets: Optional[torch.Tensor],
-                       weights: Optional[torch.Tensor], tables_dim: bool) -> torch.Tensor:
-        """``forward(..., mode=...)``: "sum" / "mean" run what a module constructed with that mode runs; "max" the max bags."""
-        if mode not in ("sum", "mean", "max"):
-            raise ValueError(f"mode must be 'sum', 'mean' or 'max', got {mode!r}")
+    def _route(self, mode: str, indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor], B: int,
+               exact: bool) -> torch.Tensor:
+        """A prepared call to the kernels that serve it: [B, D] of a module with one table, else [num_tables, B, D].  Reads
+        the mode it is given, never ``self.mode``."""
+        T = self.num_tables
         if mode == "max":
-            if weights is not None:
-                raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
-                                 "(as in torch.nn.functional.embedding_bag)")
-            if offsets is None or indices.dim() != 1:
-                indices, offsets, _ = self._fixed_bags(indices, offsets, None)
-            return self._max_pooled(indices, offsets, tables_dim)
-        own, self.mode = self.mode, mode   # (read while the call is routed only: no autograd node looks at it later)
-        try:
-            return self.forward(indices, offsets, per_sample_weights=weights)
-        finally:
-            self.mode = own
+            one = lambda k, ids, offs, w: self._max_one_table(k, ids, offs, exact)
+        elif self.padding_idx is not None:
+            if self._pad_route(indices.numel(), B, weights is not None, exact) == "partition":
+                # pad ids never reach the TT kernels: the lookup runs on the kept ids and the compacted bags
+                ids, rows, offs, kept = self._drop_padding(indices, offsets)
+                out = TTLookupFunction.apply(self, 0, B, ids, rows, offs, kept, None, None, *self.tt_cores)
+                return _BagMean.apply(out, offs) if mode == "mean" else out
+            one = lambda k, ids, offs, w: self._masked_one_table(k, ids, offs, w, mode, exact)
+        elif weights is not None:
+            one = lambda k, ids, offs, w: self._weighted_one_table(k, ids, offs, w, exact)
+        else:   # the plain bag sums (no host synchronisation wherever the lookup has none); a mean divides them by the lengths
+            sums = (self._lookup_one_table(0, B, indices, offsets, exact) if T == 1
+                    else self._lookup_tables(indices, offsets, B, exact))
+            return _BagMean.apply(sums, offsets) if mode == "mean" else sums
+        return one(0, indices, offsets, weights) if T == 1 else self._each_table(one, indices, offsets, B, weights)
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None, mode: Optional[str] = None) -> torch.Tensor:
         # `warmup` is accepted and ignored, like the reference (it reads self.warmup, :862)
-        if mode is not None:
-            return self._per_call_mode(mode, indices, offsets, per_sample_weights, True)
-        if offsets is None or indices.dim() != 1:
-            indices, offsets, per_sample_weights = self._fixed_bags(indices, offsets, per_sample_weights)
-        if self.padding_idx is not None:
-            return self._padded(indices, offsets, per_sample_weights, True)
-        if per_sample_weights is not None or self.mode != "sum":
-            return self._pooled(indices, offsets, per_sample_weights, True)
-        if not indices.is_cuda:
-            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
-        indices, offsets = indices.long().contiguous(), offsets.long().contiguous()
-        assert (offsets.numel() - 1) % self.num_tables == 0
-        B = (offsets.numel() - 1) // self.num_tables
-        if not self._fused_probe():
-            self.update_cache(indices)
-        exact = self._exact_active()
-        if self.num_tables == 1:
-            return self._lookup_one_table(0, B, indices, offsets, exact).unsqueeze(0)
-        return self._lookup_tables(indices, offsets, B, exact)
+        out = self._route(*self._prepare(indices, offsets, per_sample_weights, mode))
+        return out.unsqueeze(0) if self.num_tables == 1 else out
 
-    def _lookup_tables(self, indices: torch.Tensor, offsets: torch.Tensor, B: int, exact: bool) -> torch.Tensor:
-        """[num_tables, B, D] bag sums of a module with several tables."""
-        # every table is a window of the id list, its bounds read from `offsets` on the device (no host synchronisation) -- when the
-        # grouped kernels serve the shape; else the id list is split on the host, one plain lookup per table
-        nnz = indices.numel()
-        if (not exact and not self.use_cache and self._use_windows and nnz > 0 and B > 0
-                and _nat.window_workspace_bytes(self._shape, _nat.OP_BACKWARD, nnz, offsets.numel() - 1, B) >= 0):
-            return _TablesLookup.apply(self, B, indices, offsets, *self.tt_cores)
-        bounds = offsets[:: B].tolist()  # host sync: only this fallback of the multi-table path pays it
+    def _each_table(self, one, indices: torch.Tensor, offsets: torch.Tensor, B: int,
+                    weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Several tables where no kernel reads the table bounds on the device: the id list is split on the host (one
+        synchronisation) and ``one(table, ids, offsets, weights)`` gives each table's [B, D], stacked to [num_tables, B, D]."""
+        if B == 0:
+            return torch.zeros((self.num_tables, 0, self.embedding_dim), dtype=torch.float32, device=indices.device)
+        bounds = offsets[:: B].tolist()
         outs = []
         for k in range(self.num_tables):
             lo, hi = int(bounds[k]), int(bounds[k + 1])
             offs_k = (offsets[k * B:(k + 1) * B + 1] - lo).contiguous()
-            outs.append(self._lookup_one_table(k, B, indices[lo:hi].contiguous(), offs_k, exact))
+            outs.append(one(k, indices[lo:hi].contiguous(), offs_k, None if weights is None else weights[lo:hi]))
         return torch.stack(outs, 0)
+
+    def _lookup_tables(self, indices: torch.Tensor, offsets: torch.Tensor, B: int, exact: bool) -> torch.Tensor:
+        """[num_tables, B, D] bag sums of a module with several tables."""
+        # every table is a window of the id list, its bounds read from `offsets` on the device (no host synchronisation) -- when the
+        # grouped kernels serve the shape; else one plain lookup per table of the host-split id list
+        nnz = indices.numel()
+        if (not exact and not self.use_cache and self._use_windows and nnz > 0 and B > 0
+                and _nat.window_workspace_bytes(self._shape, _nat.OP_BACKWARD, nnz, offsets.numel() - 1, B) >= 0):
+            return _TablesLookup.apply(self, B, indices, offsets, *self.tt_cores)
+        return self._each_table(lambda k, ids, offs, w: self._lookup_one_table(k, B, ids, offs, exact), indices, offsets, B)
 
 
 class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
@@ -1363,22 +1247,6 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None, mode: Optional[str] = None) -> torch.Tensor:
-        if mode is not None:
-            return self._per_call_mode(mode, indices, offsets, per_sample_weights, False)
         # same result as the reference's ``super().forward(...)[0]`` (:960-965) without the
         # [1, B, D] view: selecting table 0 would cost a zero-fill + copy of B*D floats in backward
-        if offsets is None or indices.dim() != 1:
-            indices, offsets, per_sample_weights = self._fixed_bags(indices, offsets, per_sample_weights)
-        if self.padding_idx is not None:
-            return self._padded(indices, offsets, per_sample_weights, False)
-        if per_sample_weights is not None or self.mode != "sum":
-            return self._pooled(indices, offsets, per_sample_weights, False)
-        if not indices.is_cuda:
-            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
-        if indices.dtype != torch.int64 or not indices.is_contiguous():
-            indices = indices.long().contiguous()
-        if offsets.dtype != torch.int64 or not offsets.is_contiguous():
-            offsets = offsets.long().contiguous()
-        if self.use_cache and not self._fused_probe():
-            self.update_cache(indices)
-        return self._lookup_one_table(0, offsets.numel() - 1, indices, offsets)
+        return self._route(*self._prepare(indices, offsets, per_sample_weights, mode))

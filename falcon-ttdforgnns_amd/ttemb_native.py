@@ -337,6 +337,19 @@ def kernel_family(shape: Shape, nnz: int, B: int, ids_with_offsets: bool = True)
     return rc
 
 
+def is_grouped(shape: Shape, nnz: int, B: int, ids_with_offsets: bool = True) -> bool:
+    """Whether a lookup of this size runs on the grouped kernels (the family with bounded device-side waits, whose last
+    backward kernel leaves its verdict in the workspace header).  The one memo of that answer; launches nothing."""
+    key = ("g", _shape_key(shape), nnz, B, ids_with_offsets, path_epoch)
+    g = _size_cache.get(key)
+    if g is None:
+        if len(_size_cache) > 4096:
+            _size_cache.clear()
+        g = _size_cache[key] = nnz > 0 and (kernel_family(shape, nnz, B, ids_with_offsets) & 7) in (FAMILY_GROUPED,
+                                                                                                   FAMILY_GROUPED_WIDE)
+    return g
+
+
 def set_spin_limit(tries: int = 0) -> None:
     """Diagnostic: tries of the grouping pass's bounded device-side waits (0 = default, negative = none: every wait expires)."""
     _check(LIB.ttemb_set_spin_limit(tries))
@@ -882,18 +895,15 @@ class LeanCalls:
         self.state_key, self.state_arr = None, None
         self.state2_key, self.state2_arr = None, None   # (Adam: the second moment)
         self.grad_key, self.grad_arr = None, None
-        self.grouped: dict = {}
 
     def _entry(self, nnz: int, B: int):
         if self.epoch != path_epoch:
             self.sizes.clear()
-            self.grouped.clear()
             self.epoch = path_epoch
         e = self.sizes.get((nnz, B))
         if e is None:
             if len(self.sizes) > 1024:
                 self.sizes.clear()
-                self.grouped.clear()
             e = self.sizes[(nnz, B)] = (workspace_bytes(self.shape, OP_FORWARD, nnz, B),
                                         workspace_bytes(self.shape, OP_BACKWARD, nnz, B), plan_bytes(self.shape, nnz))
         return e
@@ -948,9 +958,8 @@ class LeanCalls:
             _check(rc)
         return plan
 
-    def backward_dense(self, cores, indices, offsets, nnz: int, B: int, d_output, grads, plan) -> bool:
-        """Dense core gradients into ``grads`` (a fixed list of tensors: their pointer array is cached).  Returns whether
-        the gradient came from the grouped kernels (the family whose last kernel leaves its verdict in the workspace header)."""
+    def backward_dense(self, cores, indices, offsets, nnz: int, B: int, d_output, grads, plan) -> None:
+        """Dense core gradients into ``grads`` (a fixed list of tensors: their pointer array is cached)."""
         _, bwd_ws, plan_n = self._entry(nnz, B)
         self.core_key, self.core_arr = self._ptrs(cores, self.core_key, self.core_arr)
         self.grad_key, self.grad_arr = self._ptrs(grads, self.grad_key, self.grad_arr)
@@ -963,10 +972,6 @@ class LeanCalls:
                                           pp, pn, _stream(d_output))
         if rc:
             _check(rc)
-        g = self.grouped.get((nnz, B))
-        if g is None:
-            g = self.grouped[(nnz, B)] = nnz > 0 and (kernel_family(self.shape, nnz, B, True) & 7) in (FAMILY_GROUPED, FAMILY_GROUPED_WIDE)
-        return g
 
     def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan, adam=None,
                  nnz_dev=None):

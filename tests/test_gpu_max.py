@@ -524,3 +524,34 @@ def test_per_call_sum_and_mean_are_the_constructed_module(nat, ops, mode, kind):
     assert bool(out_a.any()) and torch.equal(out_a, out_b)
     for x, y in zip(a.tt_cores, b.tt_cores):
         assert torch.equal(x.grad, y.grad)
+
+
+def test_per_call_mode_never_writes_the_modules_mode(nat, ops):
+    """``forward(mode=...)`` is an argument of the call, not a state of the module: a "sum" module called with "mean" and
+    with "sum", 1-D ids with offsets (8 ids in 3 bags, the middle one empty) and 2-D ids, never assigns ``mode`` -- a second
+    thread or a ``capture()`` reading it meanwhile sees the constructor's -- and its "mean" is the constructed "mean" module's
+    (the file's forward tolerance)."""
+    p, q, r = [10, 10, 10], [2, 2, 4], [4, 4]
+    writes = []
+
+    class Recording(ops.TTEmbeddingBag):
+        def __setattr__(self, name, value):
+            if name == "mode" and "mode" in self.__dict__:   # (the first assignment is the constructor's)
+                writes.append(value)
+            super().__setattr__(name, value)
+
+    ref = _emb(ops, p, q, r, "mean")
+    e = Recording(1000, 16, r, p, q, use_cache=False, sparse=False)
+    with torch.no_grad():
+        for c, c0 in zip(e.tt_cores, ref.tt_cores):
+            c.copy_(c0)
+    assert e.mode == "sum" and writes == []
+    idx = torch.tensor([3, 999, 17, 500, 3, 42, 0, 731], device="cuda")
+    offs = torch.tensor([0, 5, 5, 8], device="cuda")
+    for call in ((idx, offs), (idx.view(2, 4),)):
+        mean, total = e(*call, mode="mean"), e(*call, mode="sum")
+        assert bool(mean.any())
+        torch.testing.assert_close(total, e(*call), rtol=1e-5, atol=1e-4)
+        torch.testing.assert_close(mean, ref(*call), rtol=1e-5, atol=1e-4)
+    assert not bool(e(idx, offs, mode="mean")[1].any())   # the empty bag
+    assert writes == [] and e.mode == "sum"

@@ -202,14 +202,18 @@ def test_wide_rank_module_on_the_grouped_chain(ops, q, r, mode, wide_backward_fo
             torch.testing.assert_close(c.data[big], (b - lr * ref.grad / (ref.grad.abs() + eps))[big], rtol=0, atol=1e-4)
 
 
+@pytest.mark.parametrize("lean", [True, False])
 @pytest.mark.parametrize("optimizer", ["SGD", "EXACT_ADAGRAD"])
-def test_sparse_mode_updates_in_backward(ops, optimizer):
+def test_sparse_mode_updates_in_backward(ops, optimizer, lean):
+    """lean: the one-input bridge of the common step; not lean: the same call through the general bridge.  Each is held to
+    the reference (not to the other: the grouped kernels' float atomics promise no bit equality between two runs)."""
     torch.manual_seed(3)
     p, q, r = [7, 9, 11], [4, 5, 5], [16, 16]
     n, D = int(np.prod(p)), int(np.prod(q))
     lr, eps = 0.05, 1e-10
     emb = ops.TTEmbeddingBag(n, D, r, p, q, sparse=True, use_cache=False, weight_dist="uniform",
                              optimizer=getattr(ops.OptimType, optimizer), learning_rate=lr, eps=eps)
+    emb._use_lean = lean
     for c in emb.tt_cores:
         c.data.mul_(3.0)
     before = [c.detach().clone() for c in emb.tt_cores]
@@ -786,15 +790,17 @@ def test_single_process_data_parallel_step_skips_a_poisoned_gradient(ops):
     assert all(bool(torch.isfinite(c).all()) for c in emb.tt_cores)
 
 
-def test_bucket_accumulates_over_two_backwards_before_the_step(ops, orc):
+@pytest.mark.parametrize("lean", [True, False])
+def test_bucket_accumulates_over_two_backwards_before_the_step(ops, orc, lean):
     """Gradient accumulation with the data-parallel wrapper attached: two forward/backward passes before dp.step()
     must sum into the flat bucket (the kernels overwrite their destination; the second pass goes through scratch),
-    as autograd accumulates into .grad."""
+    as autograd accumulates into .grad.  lean / not lean: through the bucket bridge, and through the general one."""
     from ttemb_dist import TTDataParallel
     torch.manual_seed(3)
     p, q, r = [125, 140, 140], [4, 5, 5], [16, 16]
     lr = 0.2
     emb = ops.TTEmbeddingBag(2449029, 100, r, p, q, sparse=False, use_cache=False, weight_dist="normal", learning_rate=lr)
+    emb._use_lean = lean
     for c in emb.tt_cores:
         c.data.mul_(300.0)
     dp = TTDataParallel(emb)   # no process group: world size 1
