@@ -315,10 +315,10 @@ class TTLookupFunction(torch.autograd.Function):
         cached = ctx.live_cache and nnz > 0
         if m.sparse:
             state, adam = _step_call(m, table)
-            lr, eps = float(m.learning_rate), float(m.eps)
+            lr, eps = m._lr_arg(), float(m.eps)   # (a capturable module: its device word, else the float)
             if adam is not None:   # (never with a live cache: the constructor refuses that combination)
                 _nat.backward_adam(m._shape, cores, state, adam[0], adam[1], indices, rowidx, nnz, nnz_dev, B, d_output,
-                                   adam[2], m._ws, ctx.plan, offsets)
+                                   adam[2], m._ws, ctx.plan, offsets, lr if m.capturable else None)
             elif state is None:
                 _nat.backward_sgd(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, m._ws, ctx.plan, offsets)
                 if cached:
@@ -372,10 +372,11 @@ class _TablesLookup(torch.autograd.Function):
         d_output = _f32(d_output)
         T = m.num_tables
         if m.sparse:
+            lr = m._lr_arg()
             for k in range(T):
                 state, adam = _step_call(m, k)   # (Adam: one step count per table, advanced by that table's window)
                 _nat.backward_window(m._shape, _nat.core_ptrs(m.tt_cores, k), indices, offsets, k * B, B, d_output, m._ws,
-                                     opt_state=state, lr=float(m.learning_rate), eps=float(m.eps), adam=adam)
+                                     opt_state=state, lr=lr, eps=float(m.eps), adam=adam)
             return (None,) * (4 + len(m.tt_cores))
         grads = [torch.empty_like(c) for c in m.tt_cores]
         for k in range(T):
@@ -405,7 +406,7 @@ class _SparseLookup(torch.autograd.Function):
         d_output = _f32(d_output)
         state = None if m.optimizer in _SGD_LIKE else m._states()
         m._lean.backward(m._cores(), state, ctx.indices, ctx.offsets, ctx.indices.numel(), ctx.B, d_output,
-                         float(m.learning_rate), float(m.eps), ctx.plan, m._adam_lean())
+                         m._lr_arg(), float(m.eps), ctx.plan, m._adam_lean())
         return None, None, None, None, None
 
 
@@ -468,7 +469,7 @@ class _ExactLookup(torch.autograd.Function):
         if m.sparse:
             state, adam = _step_call(m, table)
             _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, opt_state=state,
-                                lr=float(m.learning_rate), eps=float(m.eps), adam=adam)
+                                lr=m._lr_arg(), eps=float(m.eps), adam=adam)
             return (None,) * (n_fixed + len(m.tt_cores))
         m._last_bwd_grouped = False   # no bounded device-side waits: nothing in the workspace header to look at
         full = _deliver_dense(m, table, m.num_tables == 1,
@@ -607,7 +608,12 @@ class CapturedLookup:
     need.  One launch (``ttemb_stage_call``) puts the call into the static buffers, pads the offsets with empty bags and
     leaves the id count in a device word the captured kernels read; the result is ``output[:B_live]``, a view of the static
     buffer.  The launches are sized by the capacity, so pick one near the largest frontier.  Offsets come with each call,
-    none at capture.  Not in exact mode: the exact backward takes no device id count.  DESIGN.md §4.11."""
+    none at capture.  Not in exact mode: the exact backward takes no device id count.  DESIGN.md §4.11.
+
+    The learning rate: a captured backward of a plain module bakes it in (a call after ``set_learning_rate`` raises:
+    capture again).  A module built with ``capturable=True`` hands the graphs the ADDRESS of its device word ``lr_dev``
+    instead: every call first brings the word up to ``module.learning_rate`` (one ``fill_`` when it changed, nothing
+    otherwise), then replays -- a scheduler that changes the rate every step re-captures nothing.  DESIGN.md §4.12."""
 
     def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, offsets: Optional[torch.Tensor] = None,
                  variable: bool = False) -> None:
@@ -642,7 +648,7 @@ class CapturedLookup:
         self._lean = _nat.LeanCalls(module._shape, _nat.Workspace())   # private workspace: pinned for the graphs' lifetime
         cores = module._cores()
         state = None if module.optimizer in _SGD_LIKE else module._states()
-        lr, eps = float(module.learning_rate), float(module.eps)
+        lr, eps = module._lr_arg(), float(module.eps)   # (capturable: the device word, brought up to date; held by address)
         # Adam: b1, b2 and the weight decay are baked like lr / eps; the step count is a device word the graph advances
         adam = module._adam_lean()
         self._adam_key = module._adam_key()
@@ -689,13 +695,15 @@ class CapturedLookup:
             with torch.no_grad():
                 for t, t0 in zip((*cores, *state, *adam[0], module.adam_step), saved):
                     t.copy_(t0)
-        self._lr, self._eps = lr, eps
+        self._lr, self._eps = (None if module.capturable else lr), eps
         self._baked = self._pointers()
 
     def _pointers(self) -> tuple:
-        """What the graphs hold by address: the cores and the optimiser state."""
+        """What the graphs hold by address: the cores, the optimiser state and a capturable module's rate word."""
         m = self.module
         ptrs = tuple(c.data_ptr() for c in m._cores())
+        if m.capturable:
+            ptrs += (m.lr_dev.data_ptr(),)
         if m.optimizer not in _SGD_LIKE:
             ptrs += tuple(st.data_ptr() for st in m._states())
         if m.optimizer == OptimType.ADAM:
@@ -708,12 +716,18 @@ class CapturedLookup:
             # after cache_populate() the eager module serves and trains the hot ids in cache_weight; the captured graphs
             # read and update the TT cores only -- the two would diverge silently
             raise RuntimeError("the row cache went live after capture(): captured lookups do not cover a live cache")
-        if float(m.learning_rate) != self._lr or float(m.eps) != self._eps or m._adam_key() != self._adam_key:
+        if m.capturable != (self._lr is None):
+            raise RuntimeError("module.capturable was changed after capture(): capture() again")
+        # (a capturable module: the rate is not part of the graphs -- _adam_key() leaves it out, too)
+        if ((self._lr is not None and float(m.learning_rate) != self._lr) or float(m.eps) != self._eps
+                or m._adam_key() != self._adam_key):
             raise RuntimeError("learning rate / eps are part of the captured backward: capture() again after changing them "
                                "(with OptimType.ADAM also betas, weight_decay and decoupled_weight_decay)")
         if self._pointers() != self._baked:
             raise RuntimeError("tt_cores / optimizer_state were re-allocated after capture() (.to(), .data = ..., "
                                "load_state_dict into new storage): capture() again")
+        if self._lr is None:
+            m._refresh_lr()   # one fill_ on this stream when learning_rate changed since the last call; no synchronisation
         if self.variable:
             return self._call_variable(indices, offsets)
         if m.use_cache:   # warm-up: the LFU statistics of a captured step count like those of an eager one
@@ -778,8 +792,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
                  padding_idx: Optional[int] = None, betas=(0.9, 0.999), weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False) -> None:
+                 decoupled_weight_decay: bool = False, capturable: bool = False) -> None:
         super().__init__()
+        if capturable and use_cache and sparse:
+            raise ValueError(
+                "use_cache=True with sparse=True and capturable=True is not supported: once cache_populate() makes the row "
+                "cache live the cached rows are trained by a per-row kernel that takes the learning rate by value, not from "
+                "the device word, and capture() does not cover a live cache anyway.  Use use_cache=False, or capturable=False "
+                "with the cache.")
         if optimizer == OptimType.ADAM:
             if not (0.0 <= float(betas[0]) < 1.0 and 0.0 <= float(betas[1]) < 1.0):
                 raise ValueError(f"betas must lie in [0, 1), got {tuple(betas)}")
@@ -852,6 +872,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
             for c in self.tt_cores:
                 self.optimizer_state_v.append(torch.zeros_like(c.data))
             self.register_buffer("adam_step", torch.zeros((num_tables, 4), device=dev, dtype=torch.int32))
+        # capturable (torch.optim's name): the rate of every fused step is read from the device word `lr_dev`, which captured
+        # graphs hold by address.  Non-persistent: the state_dict keys of every optimiser stay what they are.  `_lr_mirror`: the
+        # float last written to the word by the module itself, None = unknown (the word was set from a tensor).
+        self.capturable = bool(capturable)
+        self._lr_mirror: Optional[float] = None
+        if self.capturable:
+            self._lr_mirror = float(learning_rate)
+            self.register_buffer("lr_dev", torch.full((1,), self._lr_mirror, device=dev, dtype=torch.float32), persistent=False)
         self.reset_parameters(weight_dist)
         self.use_cache = use_cache
         if use_cache:
@@ -908,8 +936,43 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         from ttemb_init import init_cores
         init_cores(self, weight_dist)
 
-    def set_learning_rate(self, lr: float) -> None:
+    def set_learning_rate(self, lr) -> None:
+        """The rate of the steps that follow: a float -- or, on a ``capturable=True`` module, a float32 device tensor of one
+        element.  A float is only noted here (``learning_rate`` is a plain attribute and may be assigned directly, too); a
+        capturable module compares it with the last value it wrote to ``lr_dev`` at the start of every eager backward and
+        every captured call and issues one ``fill_`` on the current stream when they differ -- no synchronisation, and
+        nothing at all while the rate is unchanged.  A tensor is copied device-to-device into ``lr_dev`` right here, on the
+        current stream, without a host synchronisation; ``learning_rate`` then holds that tensor (the host does not know
+        the value) and the module does no refresh of its own until a float is set again.  The value in the word is not
+        range-checked: a negative or NaN rate does what the arithmetic does.  DESIGN.md §4.12."""
+        if isinstance(lr, torch.Tensor):
+            if not self.capturable:
+                raise TypeError("set_learning_rate(tensor) needs a module built with capturable=True (this one takes its "
+                                "rate on the host: pass a float)")
+            if lr.dtype != torch.float32 or lr.numel() != 1 or lr.device != self.lr_dev.device:
+                raise ValueError(f"a tensor learning rate must be float32 with one element on {self.lr_dev.device}, got "
+                                 f"{lr.dtype} {list(lr.shape)} on {lr.device}")
+            with torch.no_grad():
+                self.lr_dev.copy_(lr.detach().reshape(1))
+            self._lr_mirror = None
         self.learning_rate = lr
+
+    def _refresh_lr(self) -> None:
+        """Bring ``lr_dev`` up to a float ``learning_rate`` (capturable modules; see ``set_learning_rate``)."""
+        lr = self.learning_rate
+        if isinstance(lr, torch.Tensor):   # set from a tensor: the word already holds it
+            return
+        lr = float(lr)
+        if lr != self._lr_mirror:
+            self._buffers["lr_dev"].fill_(lr)
+            self._lr_mirror = lr
+
+    def _lr_arg(self):
+        """What a fused step takes as its rate: the float, or a capturable module's device word (brought up to date)."""
+        if not self.capturable:
+            return float(self.learning_rate)
+        self._refresh_lr()
+        return self._buffers["lr_dev"]
 
     def get_params(self):
         params = self.tt_cores
@@ -970,8 +1033,9 @@ class TableBatchedTTEmbeddingBag(nn.Module):
     def _adam_key(self) -> Optional[tuple]:
         if self.optimizer != OptimType.ADAM:
             return None
-        return (float(self.learning_rate), float(self.eps), self.betas[0], self.betas[1], float(self.weight_decay),
-                bool(self.decoupled_weight_decay))
+        # (capturable: the kernels read the rate from lr_dev and ignore the one in ttemb_adam_t)
+        return (0.0 if self.capturable else float(self.learning_rate), float(self.eps), self.betas[0], self.betas[1],
+                float(self.weight_decay), bool(self.decoupled_weight_decay))
 
     def _adam_params(self):
         """``ttemb_adam_t`` of the current hyper-parameters (rebuilt when one of them changed)."""
@@ -1238,12 +1302,12 @@ class TTEmbeddingBag(TableBatchedTTEmbeddingBag):
                  weight_dist: str = "approx-normal", enforce_embedding_dim: bool = False,
                  batch_count: int = 1000, *, deterministic: Optional[bool] = None, mode: str = "sum",
                  padding_idx: Optional[int] = None, betas=(0.9, 0.999), weight_decay: float = 0.0,
-                 decoupled_weight_decay: bool = False) -> None:
+                 decoupled_weight_decay: bool = False, capturable: bool = False) -> None:
         super().__init__(1, num_embeddings, embedding_dim, tt_ranks, tt_p_shapes, tt_q_shapes, optimizer,
                          learning_rate, eps, sparse, use_cache, cache_size, hashtbl_size, weight_dist,
                          enforce_embedding_dim, batch_count, deterministic=deterministic, mode=mode,
                          padding_idx=padding_idx, betas=betas, weight_decay=weight_decay,
-                         decoupled_weight_decay=decoupled_weight_decay)
+                         decoupled_weight_decay=decoupled_weight_decay, capturable=capturable)
 
     def forward(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None, warmup: bool = True, *,
                 per_sample_weights: Optional[torch.Tensor] = None, mode: Optional[str] = None) -> torch.Tensor:

@@ -636,10 +636,12 @@ __global__ void zero_rows_kernel(const int64_t* __restrict__ offsets, int64_t B,
   for (int c = 0; c * 4 < D; ++c) o[c] = z;
 }
 
-__global__ void sgd_step_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t n, float lr, const float* __restrict__ skip) {
+__global__ void sgd_step_kernel(float* __restrict__ w, const float* __restrict__ g, int64_t n, float lr_arg, const float* __restrict__ lr_dev,
+                                const float* __restrict__ skip) {
   // (ttemb_sgd_step_guarded: some rank's gradient came from a poisoned plan.  The word is tested BIT-wise: an all-reduced float
   //  count (k.0f) and the uint32 poison word of a workspace header (1) both read non-zero, +0.0f and 0u both zero)
   if (skip != nullptr && *reinterpret_cast<const uint32_t*>(skip) != 0u) return;
+  const float lr = step_lr(lr_dev, lr_arg);
   int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i + 3 < n) {
     float4 wv = *reinterpret_cast<float4*>(w + i);
@@ -652,9 +654,10 @@ __global__ void sgd_step_kernel(float* __restrict__ w, const float* __restrict__
 }
 
 __global__ void adagrad_step_kernel(float* __restrict__ w, float* __restrict__ st,
-                                    const float* __restrict__ g, int64_t n, float lr, float eps) {
+                                    const float* __restrict__ g, int64_t n, float lr_arg, const float* __restrict__ lr_dev, float eps) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
+  const float lr = step_lr(lr_dev, lr_arg);
   const float gv = g[i];
   const float s2 = st[i] + gv * gv;
   st[i] = s2;
@@ -682,8 +685,11 @@ __global__ void adam_prepare_kernel(AdamPrep a) {
 
 // one launch for every core: blockIdx.y selects the core
 // `skip`: the poison word a grouped backward of this call left in the workspace header (FusedUpdate::poison_out), or null
-__global__ void fused_step_kernel(Seg3 seg, float lr, float eps, int adagrad, const uint32_t* __restrict__ skip, AdamSeg ad) {
+// `lr_dev`: the rate as a device word (null: `lr_arg`), read once per thread at the top
+__global__ void fused_step_kernel(Seg3 seg, float lr_arg, const float* __restrict__ lr_dev, float eps, int adagrad,
+                                  const uint32_t* __restrict__ skip, AdamSeg ad) {
   if (skip != nullptr && *skip != 0u) return;   // the gradients are NaN and the host hears of it: parameters stay as they are
+  const float lr = step_lr(lr_dev, lr_arg);
   const int t = blockIdx.y;
   float* __restrict__ w = seg.w[t];
   const float* __restrict__ g = seg.g[t];
@@ -743,21 +749,23 @@ __global__ void fused_step_kernel(Seg3 seg, float lr, float eps, int adagrad, co
   }
 }
 
-static int run_sgd(float* w, const float* g, int64_t n, float lr, hipStream_t st, const float* skip = nullptr) {
+static int run_sgd(float* w, const float* g, int64_t n, float lr, hipStream_t st, const float* skip = nullptr,
+                   const float* lr_dev = nullptr) {
   if (n <= 0) return TTEMB_OK;
   if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g)) & 15)
     return fail(TTEMB_E_BADARG, "sgd_step: buffers must be 16-byte aligned");
   const int threads = 256;
   const int64_t blocks = ((n + 3) / 4 + threads - 1) / threads;
-  hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, g, n, lr, skip);
+  hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, g, n, lr, lr_dev, skip);
   return check_hip(hipGetLastError(), "sgd_step_kernel");
 }
 
-static int run_adagrad(float* w, float* state, const float* g, int64_t n, float lr, float eps, hipStream_t st) {
+static int run_adagrad(float* w, float* state, const float* g, int64_t n, float lr, float eps, hipStream_t st,
+                       const float* lr_dev = nullptr) {
   if (n <= 0) return TTEMB_OK;
   const int threads = 256;
   const int64_t blocks = (n + threads - 1) / threads;
-  hipLaunchKernelGGL(adagrad_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, state, g, n, lr, eps);
+  hipLaunchKernelGGL(adagrad_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, state, g, n, lr, lr_dev, eps);
   return check_hip(hipGetLastError(), "adagrad_step_kernel");
 }
 
@@ -813,7 +821,7 @@ int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long lo
   if (rc) return rc;
   long long blocks = (nmax / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
-  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)T), dim3(256), 0, st, seg, upd.lr, upd.eps, 0, skip, ad);
+  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)T), dim3(256), 0, st, seg, upd.lr, upd.lr_dev, upd.eps, 0, skip, ad);
   return check_hip(hipGetLastError(), "fused_step_kernel (adam)");
 }
 
@@ -1185,7 +1193,8 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
                           const int64_t* indices, const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
                           const int32_t* nnz_dev, int64_t B, const float* d_output, float lr, float eps,
                           void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
-                          void* stream, const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr) {
+                          void* stream, const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr,
+                          const float* lr_dev = nullptr) {
   Entry e;
   int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
@@ -1224,6 +1233,7 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
     upd.lr = lr;
     upd.eps = eps;
   }
+  upd.lr_dev = lr_dev;
   rc = backward_into(r, ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, gp, rest_ws, rest, plan, plan_bytes, e.st,
                      e.header, fused ? &upd : nullptr);
   if (rc || fused) return rc;
@@ -1256,7 +1266,7 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   // (a grouped backward left its verdict in the header's poison word: a poisoned plan leaves the parameters alone)
   AdamSeg no_adam;
   memset(&no_adam, 0, sizeof(no_adam));
-  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, e.st, seg, lr, eps,
+  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, e.st, seg, lr, lr_dev, eps,
                      opt_state ? 1 : 0, header_skip, no_adam);
   return check_hip(hipGetLastError(), "fused_step_kernel");
 }
@@ -1337,7 +1347,7 @@ int ttemb_forward_window(const ttemb_shape_t* shape, const float* const* cores, 
 static int backward_window(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, float* const* d_cores,
                            const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B,
                            const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream,
-                           const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr) {
+                           const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr, const float* lr_dev = nullptr) {
   Entry e;
   int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
@@ -1367,6 +1377,7 @@ static int backward_window(const ttemb_shape_t* shape, float* const* cores, floa
       upd.lr = lr;
       upd.eps = eps;
     }
+    upd.lr_dev = lr_dev;
   }
   return launch_backward_window_fast3(ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, d_output, dp, e.ws, e.ws_bytes, e.st,
                                       d_cores == nullptr ? &upd : nullptr, e.header);
@@ -1469,6 +1480,81 @@ int ttemb_adagrad_step(float* weights, float* state, const float* grads, int64_t
   ApiRange api_range("ttemb_adagrad_step");
   if (n > 0 && (weights == nullptr || grads == nullptr || state == nullptr)) return fail(TTEMB_E_BADARG, "null buffer");
   return run_adagrad(weights, state, grads, n, lr, eps, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the step of a capturable caller: the learning rate is a device word (include/ttemb.h "Device-resident learning rate") ----
+// what every ttemb_*_step* call starts with: a descriptor the kernels can take.  `flat`: the state pointers are the call's own
+// arguments, the descriptor's are not looked at.  Fills `adam` for TTEMB_STEP_ADAM (the descriptor's hyper-parameters with
+// their lr ignored: 0 stands in for it, every kernel reads the word).
+static int step_args(const ttemb_step_t* step, int32_t* adam_step, bool flat, FusedUpdate* adam) {
+  if (step == nullptr) return fail(TTEMB_E_BADARG, "step: null descriptor");
+  if (step->kind != TTEMB_STEP_SGD && step->kind != TTEMB_STEP_ADAGRAD && step->kind != TTEMB_STEP_ADAM)
+    return fail(TTEMB_E_BADARG, "step: kind %d is none of TTEMB_STEP_SGD / _ADAGRAD / _ADAM", (int)step->kind);
+  if (step->lr_dev == nullptr) return fail(TTEMB_E_BADARG, "step: lr_dev is null (the by-value calls take the rate on the host)");
+  if (reinterpret_cast<uintptr_t>(step->lr_dev) & 15) return fail(TTEMB_E_BADARG, "step: lr_dev must be 16-byte aligned");
+  if (step->kind == TTEMB_STEP_ADAGRAD && !flat && step->state == nullptr) return fail(TTEMB_E_BADARG, "step: state is null (Adagrad)");
+  if (step->kind != TTEMB_STEP_ADAM) return TTEMB_OK;
+  if (!flat && (step->state == nullptr || step->state2 == nullptr)) return fail(TTEMB_E_BADARG, "step: state / state2 is null (Adam's moments)");
+  if (step->adam == nullptr) return fail(TTEMB_E_BADARG, "step: adam is null (the hyper-parameters)");
+  ttemb_adam_t hp = *step->adam;
+  hp.lr = 0.f;
+  memset(adam, 0, sizeof(*adam));
+  int rc = adam_fill(&hp, adam_step, adam);
+  if (rc) return rc;
+  adam->lr_dev = step->lr_dev;
+  return TTEMB_OK;
+}
+
+int ttemb_backward_step(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* rowidx,
+                        const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, const float* d_output,
+                        const ttemb_step_t* step, void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
+                        void* stream) {
+  ApiRange api_range("ttemb_backward_step");
+  FusedUpdate adam;
+  int rc = step_args(step, step != nullptr ? step->adam_step : nullptr, false, &adam);
+  if (rc) return rc;
+  const bool is_adam = step->kind == TTEMB_STEP_ADAM;
+  return fused_backward(shape, cores, step->kind == TTEMB_STEP_SGD ? nullptr : step->state, indices, rowidx, offsets, nnz, nnz_dev, B,
+                        d_output, 0.f, step->kind == TTEMB_STEP_ADAGRAD ? step->eps : 0.f, workspace, workspace_bytes, plan, plan_bytes,
+                        stream, is_adam ? &adam : nullptr, is_adam ? step->state2 : nullptr, step->lr_dev);
+}
+
+int ttemb_backward_step_window(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets,
+                               int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, const float* d_output,
+                               const ttemb_step_t* step, void* workspace, int64_t workspace_bytes, void* stream) {
+  ApiRange api_range("ttemb_backward_step_window");
+  FusedUpdate adam;
+  int rc = step_args(step, step != nullptr ? step->adam_step : nullptr, false, &adam);
+  if (rc) return rc;
+  const bool is_adam = step->kind == TTEMB_STEP_ADAM;
+  return backward_window(shape, cores, step->kind == TTEMB_STEP_SGD ? nullptr : step->state, nullptr, indices, offsets, nnz, bags_total,
+                         bag0, B, d_output, 0.f, step->kind == TTEMB_STEP_ADAGRAD ? step->eps : 0.f, workspace, workspace_bytes, stream,
+                         is_adam ? &adam : nullptr, is_adam ? step->state2 : nullptr, step->lr_dev);
+}
+
+int ttemb_flat_step(float* weights, float* state, float* state2, int32_t* adam_step, const float* grads, int64_t n, float grad_scale,
+                    const ttemb_step_t* step, const float* skip, void* stream) {
+  ApiRange api_range("ttemb_flat_step");
+  if (n < 0) return fail(TTEMB_E_BADARG, "negative n");
+  FusedUpdate upd;
+  int rc = step_args(step, adam_step, true, &upd);
+  if (rc || n == 0) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (weights == nullptr || grads == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
+  if (step->kind == TTEMB_STEP_ADAM) {
+    if (state == nullptr || state2 == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
+    upd.w[0] = weights;
+    upd.st[0] = state;
+    upd.v[0] = state2;
+    const long long nn = n;
+    return run_adam_arrays(upd, &grads, &nn, 1, grad_scale, reinterpret_cast<const uint32_t*>(skip), st);
+  }
+  // (SGD / Adagrad: the by-value calls have no gradient scale; Adagrad has no skip word)
+  if (grad_scale != 1.f) return fail(TTEMB_E_BADARG, "flat step: grad_scale is Adam's (pass 1 for SGD / Adagrad)");
+  if (step->kind == TTEMB_STEP_SGD) return run_sgd(weights, grads, n, 0.f, st, skip, step->lr_dev);
+  if (state == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
+  if (skip != nullptr) return fail(TTEMB_E_BADARG, "flat step: the Adagrad step takes no skip word");
+  return run_adagrad(weights, state, grads, n, 0.f, step->eps, st, step->lr_dev);
 }
 
 static int cache_update(const int64_t* indices, int64_t nnz, int64_t* hashtbl, int64_t* cache_freq, int64_t H, bool one_sweep,

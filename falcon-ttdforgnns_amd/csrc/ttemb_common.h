@@ -100,6 +100,10 @@ struct FusedUpdateK {
   float* w[TTEMB_MAX_CORES];
   float* st[TTEMB_MAX_CORES];   // Adagrad state / Adam's first moment, or null for SGD
   float lr, eps;
+  // The learning rate as a device word (null: the by-value `lr` above, the arithmetic unchanged).  Every stepping kernel reads
+  // it once, at its top (a uniform load), and no kernel writes it: a captured backward holds the ADDRESS, so the rate of a
+  // replay is whatever the word holds then (include/ttemb.h "Device-resident learning rate").  16-byte aligned.
+  const float* lr_dev;
   // Adam (v[0] != null; st = the first moment m, v = the second): the step words (see AdamPrep) and the hyper-parameters
   float* v[TTEMB_MAX_CORES];
   uint32_t* step;
@@ -142,6 +146,8 @@ __device__ __forceinline__ void adam_prepare(const AdamPrep& a) {
 struct AdamCoef {
   float step_size, inv_sqrt_bc2;
 };
+// the rate a stepping kernel applies: the device word when there is one, else the by-value argument
+__device__ __forceinline__ float step_lr(const float* __restrict__ lr_dev, float lr_arg) { return lr_dev != nullptr ? *lr_dev : lr_arg; }
 // One element of the Adam / AdamW step (torch.optim.Adam / AdamW without amsgrad).  A zero denominator (v = 0 and eps = 0: an
 // element that has never seen a gradient) leaves w alone instead of dividing 0 by 0.
 __device__ __forceinline__ void adam_element(float& w, float& m, float& v, float g, const AdamCoef& c, float lr, float eps, float b1,

@@ -381,7 +381,9 @@ __global__ __launch_bounds__(kExNT) void exact_fixup_kernel(const int32_t* __res
 
 // the fused optimisers: touched rows only, every other row and its state stay as they are
 __global__ __launch_bounds__(kExNT) void exact_sgd_kernel(float* __restrict__ W, const float* __restrict__ G,
-                                                          const uint8_t* __restrict__ touched, int64_t rows, int S, float lr) {
+                                                          const uint8_t* __restrict__ touched, int64_t rows, int S, float lr_arg,
+                                                          const float* __restrict__ lr_dev) {
+  const float lr = step_lr(lr_dev, lr_arg);
   for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
     if (!touched[r]) continue;
     for (int e = threadIdx.x; e < S; e += kExNT) W[r * S + e] -= lr * G[r * S + e];
@@ -390,7 +392,9 @@ __global__ __launch_bounds__(kExNT) void exact_sgd_kernel(float* __restrict__ W,
 
 __global__ __launch_bounds__(kExNT) void exact_adagrad_kernel(float* __restrict__ W, float* __restrict__ state,
                                                               const float* __restrict__ G, const uint8_t* __restrict__ touched,
-                                                              int64_t rows, int S, float lr, float eps) {
+                                                              int64_t rows, int S, float lr_arg, const float* __restrict__ lr_dev,
+                                                              float eps) {
+  const float lr = step_lr(lr_dev, lr_arg);
   for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
     if (!touched[r]) continue;
     for (int e = threadIdx.x; e < S; e += kExNT) {
@@ -679,7 +683,7 @@ int ex_check_common(const ttemb_shape_t* shape, ExShape* s, const int64_t* indic
 
 int ex_backward(int op, const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, const int64_t* indices,
                 const int64_t* offsets, int64_t nnz, int64_t B, const float* d_output, float* const* d_cores, float lr,
-                float eps, void* workspace, int64_t workspace_bytes, void* stream) {
+                float eps, void* workspace, int64_t workspace_bytes, void* stream, const float* lr_dev = nullptr) {
   ExShape s;
   int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
   if (rc) return rc;
@@ -778,20 +782,20 @@ int ex_backward(int op, const ttemb_shape_t* shape, float* const* cores, float* 
     const int64_t rows = k == 0 ? s.mpa : s.mpb;
     const int S = k == 0 ? s.mRa * s.mqa * s.mRm : s.mRm * s.mqb * s.mRs;
     if (op == kExSgd)
-      hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], mgrad[k], mtouched[k], rows, S, lr);
+      hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], mgrad[k], mtouched[k], rows, S, lr, lr_dev);
     else
       hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], opt_state[t], mgrad[k],
-                         mtouched[k], rows, S, lr, eps);
+                         mtouched[k], rows, S, lr, lr_dev, eps);
   }
   for (int c = 0; c < 3; ++c) {
     if (tcore[c] < 0) continue;
     float* W = cores[tcore[c]];
     if (op == kExSgd)
       hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(s.p[c])), dim3(kExNT), 0, st, W, grad[c], touched[c],
-                         (int64_t)s.p[c], s.s[c], lr);
+                         (int64_t)s.p[c], s.s[c], lr, lr_dev);
     else
       hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(s.p[c])), dim3(kExNT), 0, st, W, opt_state[tcore[c]], grad[c],
-                         touched[c], (int64_t)s.p[c], s.s[c], lr, eps);
+                         touched[c], (int64_t)s.p[c], s.s[c], lr, lr_dev, eps);
   }
   return check_hip(hipGetLastError(), "exact optimiser kernel");
 }
@@ -879,18 +883,22 @@ int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores
                      workspace_bytes, stream);
 }
 
-int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
-                              int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
-                              const float* d_output, const ttemb_adam_t* hp, void* workspace, int64_t workspace_bytes,
-                              const void* plan, int64_t plan_bytes, void* stream) {
-  (void)plan;
-  (void)plan_bytes;
+// (lr_dev != null: the rate is that device word and hp's lr is not looked at)
+static int adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                      int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
+                      const float* d_output, const ttemb_adam_t* hp_in, void* workspace, int64_t workspace_bytes,
+                      void* stream, const float* lr_dev) {
+  if (hp_in == nullptr) return fail(TTEMB_E_BADARG, "adam: null hyper-parameters / step words");
+  ttemb_adam_t hp_copy = *hp_in;
+  if (lr_dev != nullptr) hp_copy.lr = 0.f;
+  const ttemb_adam_t* hp = &hp_copy;
   ExShape s;
   int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
   if (rc) return rc;
   FusedUpdate upd;
   memset(&upd, 0, sizeof(upd));
   if ((rc = adam_fill(hp, step, &upd))) return rc;
+  upd.lr_dev = lr_dev;
   if (cores == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exact mode: null cores / moments");
   if (nnz == 0) return TTEMB_OK;   // a call without ids is a no-op (t stays)
   // the dense exact gradient into scratch behind the exact workspace, then the elementwise step (it has no order)
@@ -914,6 +922,40 @@ int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, f
   rc = ex_backward(kExDense, shape, cores, nullptr, indices, offsets, nnz, B, d_output, grads, 0.0f, 0.0f, workspace, base, stream);
   if (rc) return rc;
   return run_adam_arrays(upd, g, n, shape->T, 1.f, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
+                              int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
+                              const float* d_output, const ttemb_adam_t* hp, void* workspace, int64_t workspace_bytes,
+                              const void* plan, int64_t plan_bytes, void* stream) {
+  (void)plan;
+  (void)plan_bytes;
+  return adam_exact(shape, cores, exp_avg, exp_avg_sq, step, indices, offsets, nnz, B, d_output, hp, workspace, workspace_bytes, stream,
+                    nullptr);
+}
+
+int ttemb_backward_step_exact(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets,
+                              int64_t nnz, int64_t B, const float* d_output, const ttemb_step_t* step, void* workspace,
+                              int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream) {
+  (void)plan;
+  (void)plan_bytes;
+  if (step == nullptr) return fail(TTEMB_E_BADARG, "step: null descriptor");
+  if (step->lr_dev == nullptr) return fail(TTEMB_E_BADARG, "step: lr_dev is null (the by-value calls take the rate on the host)");
+  if (reinterpret_cast<uintptr_t>(step->lr_dev) & 15) return fail(TTEMB_E_BADARG, "step: lr_dev must be 16-byte aligned");
+  switch (step->kind) {
+    case TTEMB_STEP_SGD:
+      return ex_backward(kExSgd, shape, cores, nullptr, indices, offsets, nnz, B, d_output, nullptr, 0.0f, 0.0f, workspace,
+                         workspace_bytes, stream, step->lr_dev);
+    case TTEMB_STEP_ADAGRAD:
+      return ex_backward(kExAdagrad, shape, cores, step->state, indices, offsets, nnz, B, d_output, nullptr, 0.0f, step->eps,
+                         workspace, workspace_bytes, stream, step->lr_dev);
+    case TTEMB_STEP_ADAM:
+      if (step->state == nullptr || step->state2 == nullptr) return fail(TTEMB_E_BADARG, "step: state / state2 is null (Adam's moments)");
+      return adam_exact(shape, cores, step->state, step->state2, step->adam_step, indices, offsets, nnz, B, d_output, step->adam,
+                        workspace, workspace_bytes, stream, step->lr_dev);
+    default:
+      return fail(TTEMB_E_BADARG, "step: kind %d is none of TTEMB_STEP_SGD / _ADAGRAD / _ADAM", (int)step->kind);
+  }
 }
 
 }  // extern "C"

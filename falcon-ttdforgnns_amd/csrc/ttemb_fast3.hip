@@ -2821,21 +2821,21 @@ __global__ __launch_bounds__((EpiCfg<Q0, Q1, Q2, R1, R2>::WAVES * 64)) void fast
 // non-empty groups; dG1 = sum of the per-slice slabs.  A workgroup owns 32 consecutive outputs; its 8 lane
 // rows split the terms, so every load instruction reads 128 contiguous bytes per row and many
 // are in flight; the 8 partial sums meet in LDS.  Every output is written exactly once.
-__device__ __forceinline__ void finalize_emit(const FusedUpdateK& upd, const AdamCoef& ac, int t, float* __restrict__ grad, int idx, float g) {
+__device__ __forceinline__ void finalize_emit(const FusedUpdateK& upd, const AdamCoef& ac, float lr, int t, float* __restrict__ grad, int idx, float g) {
   if (upd.w[0] == nullptr) {   // dense mode: the gradient itself (eps = 1: added to what an earlier piece of the call left)
     grad[idx] = upd.eps != 0.f ? grad[idx] + g : g;
   } else if (upd.st[0] == nullptr) {   // fused SGD (tt_embeddings_cuda.cu:381-397), every row
-    upd.w[t][idx] -= upd.lr * g;
+    upd.w[t][idx] -= lr * g;
   } else if (upd.v[0] != nullptr) {    // fused Adam / AdamW (include/ttemb.h "Fused Adam / AdamW"), every row
     float w = upd.w[t][idx], m = upd.st[t][idx], v = upd.v[t][idx];
-    adam_element(w, m, v, g, ac, upd.lr, upd.eps, upd.b1, upd.omb1, upd.b2, upd.omb2, upd.wd, upd.decoupled);
+    adam_element(w, m, v, g, ac, lr, upd.eps, upd.b1, upd.omb1, upd.b2, upd.omb2, upd.wd, upd.decoupled);
     upd.st[t][idx] = m;
     upd.v[t][idx] = v;
     upd.w[t][idx] = w;
   } else {                             // fused Adagrad (tt_embeddings_cuda.cu:399-419)
     const float s2 = upd.st[t][idx] + g * g;
     upd.st[t][idx] = s2;
-    upd.w[t][idx] -= upd.lr * g / (sqrtf(s2) + upd.eps);
+    upd.w[t][idx] -= lr * g / (sqrtf(s2) + upd.eps);
   }
 }
 
@@ -2859,9 +2859,10 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
   if (loud && upd.w[0] != nullptr) return;   // (wave- and grid-uniform)
   // Adam: the pending step's bias corrections, formed by one lane of an earlier kernel of this backward (AdamPrep); this launch
   // reads words 2-3 and its first thread commits t.  A skipped step (the return above) leaves t with w, m and v.
+  const float lr = step_lr(upd.lr_dev, upd.lr);   // (the device word of a capturable module, read once per workgroup; never written)
   AdamCoef ac = {0.f, 0.f};
   if (upd.v[0] != nullptr) {
-    ac.step_size = upd.lr * __uint_as_float(upd.step[2]);
+    ac.step_size = lr * __uint_as_float(upd.step[2]);
     ac.inv_sqrt_bc2 = __uint_as_float(upd.step[3]);
     if (blockIdx.x == 0 && threadIdx.x == 0) upd.step[0] = upd.step[1];
   }
@@ -2919,10 +2920,10 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
     __syncthreads();
     if (threadIdx.x < 8 && o < n0) {
       const float4 a = part4[0][xb], b = part4[1][xb], c4 = part4[2][xb], d4 = part4[3][xb];
-      finalize_emit(upd, ac, 0, dG0, o + 0, (a.x + b.x) + (c4.x + d4.x) + poison);
-      finalize_emit(upd, ac, 0, dG0, o + 1, (a.y + b.y) + (c4.y + d4.y) + poison);
-      finalize_emit(upd, ac, 0, dG0, o + 2, (a.z + b.z) + (c4.z + d4.z) + poison);
-      finalize_emit(upd, ac, 0, dG0, o + 3, (a.w + b.w) + (c4.w + d4.w) + poison);
+      finalize_emit(upd, ac, lr, 0, dG0, o + 0, (a.x + b.x) + (c4.x + d4.x) + poison);
+      finalize_emit(upd, ac, lr, 0, dG0, o + 1, (a.y + b.y) + (c4.y + d4.y) + poison);
+      finalize_emit(upd, ac, lr, 0, dG0, o + 2, (a.z + b.z) + (c4.z + d4.z) + poison);
+      finalize_emit(upd, ac, lr, 0, dG0, o + 3, (a.w + b.w) + (c4.w + d4.w) + poison);
     }
     return;
   }
@@ -2947,10 +2948,10 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
       tot.z += ((v[0].z + v[1].z) + (v[2].z + v[3].z)) + ((v[4].z + v[5].z) + (v[6].z + v[7].z));
       tot.w += ((v[0].w + v[1].w) + (v[2].w + v[3].w)) + ((v[4].w + v[5].w) + (v[6].w + v[7].w));
     }
-    finalize_emit(upd, ac, 1, dG1, o + 0, tot.x + poison);
-    finalize_emit(upd, ac, 1, dG1, o + 1, tot.y + poison);
-    finalize_emit(upd, ac, 1, dG1, o + 2, tot.z + poison);
-    finalize_emit(upd, ac, 1, dG1, o + 3, tot.w + poison);
+    finalize_emit(upd, ac, lr, 1, dG1, o + 0, tot.x + poison);
+    finalize_emit(upd, ac, lr, 1, dG1, o + 1, tot.y + poison);
+    finalize_emit(upd, ac, lr, 1, dG1, o + 2, tot.z + poison);
+    finalize_emit(upd, ac, lr, 1, dG1, o + 3, tot.w + poison);
     return;
   }
   // (dG2 outputs come first, 32 per workgroup; dG0's workgroups start at a 32-aligned output of their own)
@@ -3001,9 +3002,9 @@ __global__ __launch_bounds__(256) void fast3_finalize_kernel(GroupPlan plan, int
       const int row2 = q2 * r2;
       const int i2 = e / row2, w = e - i2 * row2;
       const int kk = w / r2, c2 = w - kk * r2;
-      finalize_emit(upd, ac, 2, dG2, i2 * row2 + c2 * q2 + kk, tot);
+      finalize_emit(upd, ac, lr, 2, dG2, i2 * row2 + c2 * q2 + kk, tot);
     } else if (e < g2_floats + n0) {
-      finalize_emit(upd, ac, 0, dG0, e - g2_floats, tot);
+      finalize_emit(upd, ac, lr, 0, dG0, e - g2_floats, tot);
     }
   }
 }

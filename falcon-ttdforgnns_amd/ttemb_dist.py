@@ -150,6 +150,9 @@ class TTDataParallel:
         """
         if self._pending is not None:
             self.flush()
+        if lr is None and isinstance(self.module.learning_rate, torch.Tensor):
+            raise RuntimeError("the module's learning rate was last set from a device tensor (set_learning_rate(tensor) on a "
+                               "capturable module): the data-parallel step takes its rate on the host -- pass step(lr=...)")
         lr = float(self.module.learning_rate if lr is None else lr)
         b = self.bucket
         if getattr(self.module, "_bucket_filled", False) and len(b.params) == self.n_cores:

@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "ttemb_backward_adam", "ttemb_backward_adam_window", "ttemb_backward_adam_exact", "ttemb_adam_step",
     "ttemb_bag_max_workspace_bytes", "ttemb_bag_max", "ttemb_bag_max_backward",
     "ttemb_stage_call",
+    "ttemb_backward_step", "ttemb_backward_step_window", "ttemb_backward_step_exact", "ttemb_flat_step",
 )
 
 
@@ -54,6 +55,41 @@ class AdamParams(ctypes.Structure):
     """Mirror of ``ttemb_adam_t``: the hyper-parameters of the fused Adam / AdamW step."""
     _fields_ = [("lr", ctypes.c_float), ("eps", ctypes.c_float), ("weight_decay", ctypes.c_float),
                 ("decoupled", ctypes.c_int32), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double)]
+
+
+class StepDesc(ctypes.Structure):
+    """Mirror of ``ttemb_step_t``: the step of a call that takes its learning rate from a device word."""
+    _fields_ = [("kind", ctypes.c_int32), ("lr_dev", ctypes.c_void_p), ("eps", ctypes.c_float), ("state", ctypes.c_void_p),
+                ("state2", ctypes.c_void_p), ("adam_step", ctypes.c_void_p), ("adam", ctypes.c_void_p)]
+
+
+STEP_SGD, STEP_ADAGRAD, STEP_ADAM = 0, 1, 2
+
+
+def _lr_word(lr: torch.Tensor) -> int:
+    if lr.dtype != torch.float32 or lr.numel() != 1 or not lr.is_cuda:
+        raise ValueError("a device learning rate is a float32 tensor of one element on a ROCm device, got "
+                         f"{lr.dtype} {list(lr.shape)} on {lr.device}")
+    return lr.data_ptr()
+
+
+def step_desc(lr: torch.Tensor, eps: float = 0.0, state=None, adam=None):
+    """``ttemb_step_t`` of a step whose rate is the device word ``lr``: SGD (no ``state``), Adagrad (``state``: a pointer
+    array or tensors) or Adam (``state`` the first moment, ``adam = (exp_avg_sq, step words, AdamParams)``; the rate in the
+    ``AdamParams`` is ignored).  Returns ``(descriptor, keep)``: ``keep`` holds what the descriptor points at."""
+    d = StepDesc()
+    d.lr_dev, d.eps = _lr_word(lr), float(eps)
+    st = None if state is None else _ptr_array(state)
+    st2 = None
+    if adam is not None:
+        st2 = _ptr_array(adam[0])
+        d.kind, d.state, d.state2 = STEP_ADAM, ctypes.addressof(st), ctypes.addressof(st2)
+        d.adam_step, d.adam = _ptr(adam[1]), ctypes.addressof(adam[2])
+    elif st is not None:
+        d.kind, d.state = STEP_ADAGRAD, ctypes.addressof(st)
+    else:
+        d.kind = STEP_SGD
+    return d, (st, st2, adam, lr)
 
 
 def make_adam(lr: float, eps: float, betas=(0.9, 0.999), weight_decay: float = 0.0, decoupled: bool = False) -> AdamParams:
@@ -161,6 +197,11 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_drop_padding.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]
     lib.ttemb_pad_weights.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp]
     lib.ttemb_stage_call.argtypes = [vp, i32, i64, vp, i32, i64, vp, i64, vp, i64, vp, vp]
+    stp = ctypes.POINTER(StepDesc)
+    lib.ttemb_backward_step.argtypes = [shp, vp, vp, vp, vp, i64, vp, i64, vp, stp, vp, i64, vp, i64, vp]
+    lib.ttemb_backward_step_window.argtypes = [shp, vp, vp, vp, i64, i64, i64, i64, vp, stp, vp, i64, vp]
+    lib.ttemb_backward_step_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, stp, vp, i64, vp, i64, vp]
+    lib.ttemb_flat_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, stp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
@@ -418,8 +459,26 @@ def backward_dense(shape: Shape, cores: Sequence[torch.Tensor], indices, rowidx,
                                         w.numel(), *_plan_args(plan), _stream(d_output)))
 
 
-def backward_sgd(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, lr: float,
+def backward_step(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, lr: torch.Tensor, ws: Workspace,
+                  plan: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None, eps: float = 0.0, state=None,
+                  adam=None) -> None:
+    """The fused step with the rate in the device word ``lr`` (``ttemb_backward_step``): SGD, Adagrad (``state``) or Adam
+    (``state`` the first moment, ``adam = (exp_avg_sq, step words, AdamParams)``)."""
+    dev = d_output.device
+    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
+    desc, keep = step_desc(lr, eps, state, adam)
+    with _on_device(dev):
+        _check(LIB.ttemb_backward_step(ctypes.byref(shape), _ptr_array(cores), _ptr(indices), _ptr(rowidx), _ptr(offsets), nnz,
+                                       _ptr(nnz_dev), B, _ptr(d_output), ctypes.byref(desc), _ptr(w), w.numel(),
+                                       *_plan_args(plan), _stream(d_output)))
+    del keep
+
+
+def backward_sgd(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, lr,
                  ws: Workspace, plan: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None) -> None:
+    """``lr``: a float, or a float32[1] device tensor (the rate is then read on the device: ``backward_step``)."""
+    if isinstance(lr, torch.Tensor):
+        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets)
     dev = d_output.device
     w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
     with _on_device(dev):
@@ -430,8 +489,10 @@ def backward_sgd(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int
 
 
 def backward_adagrad(shape: Shape, cores, opt_state, indices, rowidx, nnz: int, nnz_dev, B: int, d_output,
-                     lr: float, eps: float, ws: Workspace, plan: Optional[torch.Tensor] = None,
+                     lr, eps: float, ws: Workspace, plan: Optional[torch.Tensor] = None,
                      offsets: Optional[torch.Tensor] = None) -> None:
+    if isinstance(lr, torch.Tensor):   # (as in backward_sgd)
+        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets, eps, opt_state)
     dev = d_output.device
     w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
     with _on_device(dev):
@@ -443,9 +504,13 @@ def backward_adagrad(shape: Shape, cores, opt_state, indices, rowidx, nnz: int, 
 
 def backward_adam(shape: Shape, cores, exp_avg, exp_avg_sq, step: torch.Tensor, indices, rowidx, nnz: int, nnz_dev, B: int,
                   d_output, hp: AdamParams, ws: Workspace, plan: Optional[torch.Tensor] = None,
-                  offsets: Optional[torch.Tensor] = None) -> None:
+                  offsets: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None) -> None:
     """Fused Adam / AdamW step (``ttemb_backward_adam``): ``exp_avg`` / ``exp_avg_sq`` shaped like the cores, ``step`` the
-    int32[4] device words of ``new_adam_step``."""
+    int32[4] device words of ``new_adam_step``.  ``lr`` (a float32[1] device tensor): the rate is read on the device and
+    the one in ``hp`` ignored (``backward_step``)."""
+    if lr is not None:
+        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets, 0.0, exp_avg,
+                             (exp_avg_sq, step, hp))
     dev = d_output.device
     w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
     with _on_device(dev):
@@ -455,16 +520,37 @@ def backward_adam(shape: Shape, cores, exp_avg, exp_avg_sq, step: torch.Tensor, 
                                        _stream(d_output)))
 
 
-def adam_step(weights, exp_avg, exp_avg_sq, step: torch.Tensor, grads, hp: AdamParams, grad_scale: float = 1.0,
+def flat_step(weights, grads, lr: torch.Tensor, state=None, eps: float = 0.0, adam=None, grad_scale: float = 1.0,
               skip: Optional[torch.Tensor] = None) -> None:
+    """A flat epilogue with the rate in the device word ``lr`` (``ttemb_flat_step``): SGD, Adagrad (``state``) or Adam
+    (``state`` = exp_avg, ``adam = (exp_avg_sq, step words, AdamParams)``)."""
+    d = StepDesc()
+    d.lr_dev, d.eps = _lr_word(lr), float(eps)
+    d.kind = STEP_ADAM if adam is not None else (STEP_ADAGRAD if state is not None else STEP_SGD)
+    if adam is not None:
+        d.adam = ctypes.addressof(adam[2])
+    with _on_device(weights.device):
+        _check(LIB.ttemb_flat_step(_ptr(weights), _ptr(state), None if adam is None else _ptr(adam[0]),
+                                   None if adam is None else _ptr(adam[1]), _ptr(grads), weights.numel(), grad_scale,
+                                   ctypes.byref(d), _ptr(skip), _stream(weights)))
+
+
+def adam_step(weights, exp_avg, exp_avg_sq, step: torch.Tensor, grads, hp: AdamParams, grad_scale: float = 1.0,
+              skip: Optional[torch.Tensor] = None, lr: Optional[torch.Tensor] = None) -> None:
     """Flat Adam / AdamW epilogue (``ttemb_adam_step``): ``g = grads * grad_scale``; a non-zero device word ``skip[0]``
-    leaves weights, moments and the step count as they are."""
+    leaves weights, moments and the step count as they are.  ``lr`` (a float32[1] device tensor): the rate is read on the
+    device and the one in ``hp`` ignored."""
+    if lr is not None:
+        return flat_step(weights, grads, lr, exp_avg, adam=(exp_avg_sq, step, hp), grad_scale=grad_scale, skip=skip)
     with _on_device(weights.device):
         _check(LIB.ttemb_adam_step(_ptr(weights), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(step), _ptr(grads), weights.numel(),
                                    grad_scale, ctypes.byref(hp), _ptr(skip), _stream(weights)))
 
 
-def sgd_step(weights: torch.Tensor, grads: torch.Tensor, lr: float) -> None:
+def sgd_step(weights: torch.Tensor, grads: torch.Tensor, lr) -> None:
+    """``lr``: a float, or a float32[1] device tensor (read on the device: ``flat_step``) -- so for every flat step."""
+    if isinstance(lr, torch.Tensor):
+        return flat_step(weights, grads, lr)
     with _on_device(weights.device):
         _check(LIB.ttemb_sgd_step(_ptr(weights), _ptr(grads), weights.numel(), lr, _stream(weights)))
 
@@ -472,8 +558,10 @@ def sgd_step(weights: torch.Tensor, grads: torch.Tensor, lr: float) -> None:
 HEADER_POISON_OFFSET = 32784   # TTEMB_HEADER_POISON_OFFSET
 
 
-def sgd_step_guarded(weights: torch.Tensor, grads: torch.Tensor, lr: float, skip: torch.Tensor) -> None:
+def sgd_step_guarded(weights: torch.Tensor, grads: torch.Tensor, lr, skip: torch.Tensor) -> None:
     """``weights -= lr * grads`` unless the device float ``skip[0]`` is non-zero (then nothing is written)."""
+    if isinstance(lr, torch.Tensor):
+        return flat_step(weights, grads, lr, skip=skip)
     with _on_device(weights.device):
         _check(LIB.ttemb_sgd_step_guarded(_ptr(weights), _ptr(grads), weights.numel(), lr, _ptr(skip), _stream(weights)))
 
@@ -486,7 +574,9 @@ def poison_word(ws: "Workspace") -> Optional[torch.Tensor]:
     return ws.buf[HEADER_POISON_OFFSET:HEADER_POISON_OFFSET + 4].view(torch.int32)
 
 
-def adagrad_step(weights, state, grads, lr: float, eps: float) -> None:
+def adagrad_step(weights, state, grads, lr, eps: float) -> None:
+    if isinstance(lr, torch.Tensor):
+        return flat_step(weights, grads, lr, state, eps)
     with _on_device(weights.device):
         _check(LIB.ttemb_adagrad_step(_ptr(weights), _ptr(state), _ptr(grads), weights.numel(), lr, eps,
                                       _stream(weights)))
@@ -522,9 +612,10 @@ def forward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.T
 
 def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.Tensor, offsets: torch.Tensor, bag0: int, B: int,
                     d_output: torch.Tensor, ws: Workspace, d_cores: Optional[Sequence[torch.Tensor]] = None,
-                    opt_state: Optional[Sequence[torch.Tensor]] = None, lr: float = 0.0, eps: float = 0.0, adam=None) -> None:
+                    opt_state: Optional[Sequence[torch.Tensor]] = None, lr=0.0, eps: float = 0.0, adam=None) -> None:
     """``d_cores``: dense gradients of the window's table; else the fused step (Adagrad when ``opt_state`` is given; Adam
-    with ``adam = (exp_avg_sq, step, AdamParams)``, ``opt_state`` then the first moment)."""
+    with ``adam = (exp_avg_sq, step, AdamParams)``, ``opt_state`` then the first moment).  ``lr``: a float, or a float32[1]
+    device tensor (``ttemb_backward_step_window``: the rate is read on the device, the one of an ``AdamParams`` ignored)."""
     nnz, bags = indices.numel(), offsets.numel() - 1
     dev = d_output.device
     w = ws.get(window_workspace_bytes(shape, OP_BACKWARD, nnz, bags, B), dev)
@@ -533,6 +624,10 @@ def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.
     with _on_device(dev):
         if d_cores is not None:
             _check(LIB.ttemb_backward_dense_window(*head, *ids, _ptr_array(d_cores), _ptr(w), w.numel(), _stream(d_output)))
+        elif isinstance(lr, torch.Tensor):
+            desc, keep = step_desc(lr, eps, opt_state, adam)
+            _check(LIB.ttemb_backward_step_window(*head, *ids, ctypes.byref(desc), _ptr(w), w.numel(), _stream(d_output)))
+            del keep
         elif adam is not None:
             _check(LIB.ttemb_backward_adam_window(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
                                                   ctypes.byref(adam[2]), _ptr(w), w.numel(), _stream(d_output)))
@@ -582,10 +677,11 @@ def forward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Ten
 
 
 def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Tensor, B: int, d_output: torch.Tensor,
-                   ws: Workspace, d_cores=None, opt_state=None, lr: float = 0.0, eps: float = 0.0, adam=None) -> None:
+                   ws: Workspace, d_cores=None, opt_state=None, lr=0.0, eps: float = 0.0, adam=None) -> None:
     """Bit-reproducible backward: dense gradients into ``d_cores`` (every row written), else the fused step on the rows
     the ids touch (Adagrad when ``opt_state`` is given), or dense Adam on every row with ``adam = (exp_avg_sq, step,
-    AdamParams)`` and ``opt_state`` the first moment."""
+    AdamParams)`` and ``opt_state`` the first moment.  ``lr``: a float, or a float32[1] device tensor
+    (``ttemb_backward_step_exact``: the rate is read on the device, the one of an ``AdamParams`` ignored)."""
     nnz = indices.numel()
     dev = d_output.device
     need = exact_workspace_bytes(shape, nnz, B)
@@ -599,6 +695,10 @@ def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Te
     with _on_device(dev):
         if d_cores is not None:
             _check(LIB.ttemb_backward_dense_exact(*head, *ids, _ptr_array(d_cores), *tail))
+        elif isinstance(lr, torch.Tensor):
+            desc, keep = step_desc(lr, eps, opt_state, adam)
+            _check(LIB.ttemb_backward_step_exact(*head, *ids, ctypes.byref(desc), *tail))
+            del keep
         elif adam is not None:
             _check(LIB.ttemb_backward_adam_exact(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
                                                  ctypes.byref(adam[2]), *tail))
@@ -973,10 +1073,11 @@ class LeanCalls:
         if rc:
             _check(rc)
 
-    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr: float, eps: float, plan, adam=None,
+    def backward(self, cores, state, indices, offsets, nnz: int, B: int, d_output, lr, eps: float, plan, adam=None,
                  nnz_dev=None):
         """``adam = (exp_avg_sq, step, AdamParams)``: the fused Adam step, ``state`` then the first moment.  ``nnz_dev``: as
-        in ``forward``."""
+        in ``forward``.  ``lr``: a float, or a float32[1] device tensor -- the rate is then read on the device
+        (``ttemb_backward_step``) and the one in the ``AdamParams`` ignored."""
         _, bwd_ws, plan_n = self._entry(nnz, B)
         self.core_key, self.core_arr = self._ptrs(cores, self.core_key, self.core_arr)
         dev = d_output.device
@@ -985,7 +1086,20 @@ class LeanCalls:
         ids = indices.data_ptr() if nnz else None
         cnt = None if nnz_dev is None else nnz_dev.data_ptr()
         with _on_device(dev):
-            if adam is not None:
+            if isinstance(lr, torch.Tensor):
+                d = StepDesc()
+                d.lr_dev, d.eps = _lr_word(lr), eps
+                if state is not None:
+                    self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
+                    d.kind, d.state = STEP_ADAGRAD, ctypes.addressof(self.state_arr)
+                if adam is not None:
+                    self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
+                    d.kind, d.state2 = STEP_ADAM, ctypes.addressof(self.state2_arr)
+                    d.adam_step, d.adam = adam[1].data_ptr(), ctypes.addressof(adam[2])
+                rc = LIB.ttemb_backward_step(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, cnt, B,
+                                             d_output.data_ptr() if B else None, ctypes.byref(d), w.data_ptr(), w.numel(), pp, pn,
+                                             _stream(d_output))
+            elif adam is not None:
                 self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
                 self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
                 rc = LIB.ttemb_backward_adam(self.shape_ref, self.core_arr, self.state_arr, self.state2_arr, adam[1].data_ptr(), ids,
