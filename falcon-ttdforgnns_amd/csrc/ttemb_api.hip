@@ -883,7 +883,6 @@ static int backward_into(const Route& r, const DevShape& ds, const CorePtrs& cp,
                          const CorePtrsMut& dst, char* ws, int64_t ws_bytes, const void* plan, int64_t plan_bytes, hipStream_t st,
                          void* header, const FusedUpdate* update = nullptr) {
   if (r.kind == kPadded && update != nullptr) return fail(TTEMB_E_BADARG, "internal: a padded table writes gradients, the step follows");
-  if (r.kind == kScalar && current_path() == TTEMB_PATH_FAST3) return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
   const int64_t vb = view_bytes(r, true);   // [V | dV] / [padded cores | their gradients] in front of the grouped kernels' region
   if (vb > 0 && (ws == nullptr || ws_bytes < vb)) return fail(TTEMB_E_WORKSPACE, "backward needs room for the %s", view_name(r));
   CorePtrs c3;
@@ -1133,7 +1132,8 @@ static int forward_phase(int phase, const ttemb_shape_t* shape, const float* con
   if (r.grouped)
     return launch_forward_fast3(r.s3, c3, indices, rowidx, offsets, nnz, nnz_dev, B, output, offsets != nullptr, ws, ws_bytes, plan,
                                 plan_bytes, phase, e.st, e.header);
-  if (current_path() == TTEMB_PATH_FAST3) return fail(TTEMB_E_UNSUPPORTED, "fast3 path does not cover this shape");
+  // (a forced TTEMB_PATH_FAST3 on a table the grouped kernels do not take -- another shape, or past a size limit of
+  //  fits_shape / classify -- runs what ttemb_kernel_family and the size queries answer for it: the scalar kernels)
   return launch_forward_generic(ds, e.cp, indices, rowidx, offsets, B, nnz, nnz_dev, output, e.st);
 }
 

@@ -78,7 +78,9 @@ enum {
                                    (max(4096, p0*p1/4) ids; ranks >= 64: p0*p1/8 at 64, p0*p1/24 at 128, any at 256), else the
                                    per-bag MFMA kernels (ids + offsets), else generic */
   TTEMB_PATH_GENERIC = 1,       /* shape-generic wave-per-id kernels (T = 2..4)    */
-  TTEMB_PATH_FAST3 = 2,         /* sorted / grouped MFMA path, T == 3 only         */
+  TTEMB_PATH_FAST3 = 2,         /* sorted / grouped MFMA path at every batch size, wherever the table has it (3 cores, or a
+                                   2- / 4-core table on its 3-core view; inside the table-size limits of DESIGN.md 6c); else generic,
+                                   as ttemb_kernel_family answers */
   TTEMB_PATH_PER_BAG = 3        /* one wavefront per bag (MFMA per id) whenever the shape has it and the ids come
                                    with their offsets, at every batch size; else generic.  For crossover measurements */
 };

@@ -7,6 +7,8 @@ Tolerances (north-star: forward within 1e-4 in fp32):
   fused steps  atol 1e-5 on the updated cores
 Integer work (index split, partition, hash) is compared bit-exactly.
 """
+import hashlib
+
 import numpy as np
 import pytest
 import torch
@@ -105,6 +107,10 @@ def test_rows_of_baseline_configs(nat, name, path):
     g = load_golden(name)
     set_path(nat, path, g["q"], g["R"])
     cores = seeded_cores(g["p"], g["q"], g["R"], g["seed"], g["core_scale"])
+    h = hashlib.sha256()   # (the file carries the SHA-256 of the cores its rows were computed from, as the rank cases do)
+    for c in cores:
+        h.update(np.ascontiguousarray(c).tobytes())
+    assert h.hexdigest() == str(g["cores_sha256"]), "RNG drift: regenerate the golden vectors"
     n = g["indices"].shape[0]
     out, _ = run_forward(nat, g["p"], g["q"], g["R"], cores, g["indices"], np.arange(n + 1))
     np.testing.assert_allclose(out, g["rows"], rtol=1e-5, atol=1e-4)

@@ -32,6 +32,10 @@ for cfg in a.cfg:
         res = {}
         for name in a.paths:
             nat.set_path(PATH[name])
+            fam = nat.kernel_family(shape, N, N, True) & 7   # (a forced path runs the scalar kernels where it has none of its own)
+            want = {"generic": (0,), "fast3": (3, 4), "per_bag": (1, 2)}.get(name)
+            if want is not None and fam not in want:
+                raise SystemExit(f"{cfg} N={N}: --paths {name} would time kernel family {fam}, not its own: this table / size has none")
             def step():
                 plan = nat.new_plan(shape, N, idx.device)
                 nat.forward(shape, cores, idx, None, offs, N, None, N, out, ws, plan)
