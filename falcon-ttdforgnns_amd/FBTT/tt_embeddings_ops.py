@@ -34,7 +34,7 @@ from torch import nn
 import ttemb_native as _nat
 
 __all__ = ["OptimType", "BufferList", "tt_matrix_to_full", "suggested_tt_shapes", "TTLookupFunction",
-           "TableBatchedTTEmbeddingBag", "TTEmbeddingBag", "CapturedLookup"]
+           "TableBatchedTTEmbeddingBag", "TTEmbeddingBag", "CapturedLookup", "CapturedBags"]
 
 _LOG = logging.getLogger(__name__)
 
@@ -756,6 +756,280 @@ class CapturedLookup:
         return _ReplayLookup.apply(m._cores()[0], self, n, B_live)
 
 
+class _ReplayBags(torch.autograd.Function):
+    """Autograd node of captured bags: forward and backward are one HIP-graph replay each.  ``weights`` is the call's own
+    tensor (None without): the staged copy is what the graphs read, this input only lets autograd ask for its gradient.
+    ``n_live`` / ``B_live``: the ids and bags of the call, already staged."""
+
+    @staticmethod
+    def forward(ctx, anchor: torch.Tensor, cap: "CapturedBags", weights: Optional[torch.Tensor], n_live: int,
+                B_live: int) -> torch.Tensor:
+        ctx.cap, ctx.n_live, ctx.B_live = cap, n_live, B_live
+        ctx.w_shape = None if weights is None else weights.shape
+        cap.fwd_graph.replay()
+        return cap.output[:B_live] if cap.variable else cap.output
+
+    @staticmethod
+    def backward(ctx, d_output: torch.Tensor):
+        cap = ctx.cap
+        want_w = ctx.w_shape is not None and ctx.needs_input_grad[2]
+        if ctx.n_live == 0:   # no id: a no-op for every optimiser, Adam's t included; the weight gradient is empty
+            d_w = torch.zeros(ctx.w_shape, dtype=torch.float32, device=d_output.device) if want_w else None
+            return None, None, d_w, None, None
+        (cap.d_output[:ctx.B_live] if cap.variable else cap.d_output).copy_(d_output)
+        cap.bwd_graph.replay()
+        # (a copy: autograd may keep it as w.grad, and the next replay overwrites the static buffer)
+        d_w = cap.d_weights_out[:ctx.n_live].clone().view(ctx.w_shape) if want_w else None
+        return None, None, d_w, None, None
+
+
+class CapturedBags(CapturedLookup):
+    """``emb.capture_bags(nnz, B, mode=..., weighted=..., fanout=..., variable=...)``: the pooled calls of the module --
+    ``per_sample_weights``, ``mode="mean"`` / ``"max"``, ``padding_idx``, 2-D ``indices[rows, fanout]`` -- with forward and
+    backward (pool backward, TT backward, the module's fused step) as ONE HIP-graph replay each.  Call it like the module:
+    ``out = cap(indices, offsets=None, per_sample_weights=None)``; ``out`` is (a view of) a static buffer that the next call
+    overwrites.  The mode, ``weighted``, ``fanout`` and the module's ``padding_idx`` are fixed at capture, like the learning
+    rate of a plain module (``CapturedLookup``); the graphs are linear chains on one stream.  ``sparse=True`` modules with
+    one table and no live cache, every fused optimiser, ``capturable=True`` rate words, exact mode with ``variable=False``.
+
+    Routes, chosen once from the capacities: a mean without weights and padding is the plain lookup on the staged offsets
+    and ``ttemb_bag_mean`` in place; the unweighted unpadded sum is the plain lookup; everything else looks the ids up as
+    bags of one into a static ``rows[nnz, D]`` and pools them (``ttemb_bag_reduce_n`` with the call's weights or those of
+    ``ttemb_pad_weights_n``, ``ttemb_bag_max_n``), the backward pooling into a static ``d_rows[nnz, D]`` the lookup's
+    backward takes.  A padded call always takes these masked rows.
+
+    ``variable=True``: ``nnz`` and ``B`` are capacities; one launch (``ttemb_stage_bags``) puts ids, offsets (or, with
+    ``fanout``, the offsets it generates) and weights into the static buffers and leaves the id count in the device word every
+    captured kernel stops at.  ``variable=False``: every call has exactly the captured size.  A call without ids replays the
+    forward (zeros) and skips the backward.  The weight gradient is computed by every weighted backward and handed to
+    autograd (one copy of ``n`` floats) when the call's weights require it.  DESIGN.md §4.13."""
+
+    _MODES = ("sum", "mean", "max")
+
+    @staticmethod
+    def check_arguments(module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str], weighted: bool,
+                        fanout: Optional[int]) -> str:
+        """The argument errors of ``capture_bags``, raised before a device is touched; returns the effective mode."""
+        if mode is None:
+            mode = module.mode
+        elif mode not in CapturedBags._MODES:
+            raise ValueError(f"mode must be 'sum', 'mean' or 'max', got {mode!r}")
+        if weighted and mode != "sum":
+            raise ValueError("per_sample_weights was not None: weighted bags are only supported with mode='sum' "
+                             "(as in torch.nn.functional.embedding_bag)")
+        if not module.sparse:
+            raise ValueError("capture_bags() covers the fused-optimiser mode (sparse=True): the captured backward is the step")
+        if module.num_tables != 1:
+            raise ValueError(f"capture_bags() covers a single table, this module has {module.num_tables}")
+        if not (0 < int(nnz) < 2 ** 31 and int(B) > 0):
+            raise ValueError(f"capture_bags(): nnz and B must be positive (ids below 2^31), got nnz={nnz}, B={B}")
+        if fanout is not None and (int(fanout) <= 0 or int(nnz) != int(B) * int(fanout)):
+            raise ValueError(f"capture_bags(fanout={fanout}): nnz must equal B * fanout, got nnz={nnz}, B={B}")
+        return mode
+
+    def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str] = None, weighted: bool = False,
+                 fanout: Optional[int] = None, variable: bool = False) -> None:
+        mode = self.check_arguments(module, nnz, B, mode, weighted, fanout)
+        if module.use_cache and not module.warmup:
+            raise RuntimeError("capture_bags() with a live row cache is not supported")
+        self.module, self.nnz, self.B = module, int(nnz), int(B)
+        self.mode, self.weighted, self.variable = mode, bool(weighted), bool(variable)
+        self.fanout = None if fanout is None else int(fanout)
+        self.pad = module.padding_idx
+        self._module_mode = module.mode
+        self.exact = module._exact_active()   # exact mode: the graphs hold the exact kernels
+        if self.variable and self.exact:
+            raise RuntimeError(
+                f"capture_bags(nnz={self.nnz}, B={self.B}, variable=True) is not served in exact mode (OptimType.EXACT_SGD / "
+                "deterministic): the exact kernels take no device id count, so a call shorter than the capacity would not "
+                "reproduce the eager call bit for bit.  Use variable=False, or a module outside exact mode.")
+        nnz, B, D = self.nnz, self.B, module.embedding_dim
+        dev = module.tt_cores[0].device
+        f32 = dict(dtype=torch.float32, device=dev)
+        # which route: "plain" (the lookup pools), "mean" (the lookup, then the division), "rows" (bags of one, then the pooling)
+        self.route = "rows" if (mode == "max" or self.weighted or self.pad is not None) else ("mean" if mode == "mean" else "plain")
+        self.indices = torch.zeros(nnz, dtype=torch.int64, device=dev)
+        # until the first call: one bag that holds every id, the others empty (variable: no id at all)
+        self.offsets = torch.full((B + 1,), 0 if self.variable else nnz, dtype=torch.int64, device=dev)
+        self.offsets[0] = 0
+        if self.fanout is not None and not self.variable:
+            self.offsets.copy_(torch.arange(B + 1, dtype=torch.int64, device=dev) * self.fanout)
+        self.nnz_dev = torch.zeros(1, dtype=torch.int32, device=dev) if self.variable else None
+        self.weights = torch.zeros(nnz, **f32) if self.weighted else None
+        self.output = torch.zeros((B, D), **f32)
+        self.d_output = torch.zeros_like(self.output)
+        self.d_sums = torch.zeros_like(self.output) if self.route == "mean" else None
+        self.rows = self.d_rows = self.ones = self.pool_weights = self.argmax = self.d_weights = self.d_weights_out = None
+        if self.route == "rows":
+            # the memory this route costs: two [nnz, D] float32 buffers
+            self.rows, self.d_rows = torch.zeros((nnz, D), **f32), torch.zeros((nnz, D), **f32)
+            self.ones = torch.arange(nnz + 1, dtype=torch.int64, device=dev)   # bags of one; the count word bounds them
+            if mode == "max":
+                self.argmax = torch.full((B, D), -1, dtype=torch.int32, device=dev)
+            else:
+                # what the pooling multiplies with: the call's weights, or those ttemb_pad_weights_n makes of them
+                self.pool_weights = torch.zeros(nnz, **f32) if self.pad is not None else self.weights
+            if self.weighted:
+                self.d_weights = torch.zeros(nnz, **f32)
+                # (padded: the gradient of the masked weights goes through the mask once more, as the eager _PadWeights does)
+                self.d_weights_out = torch.zeros(nnz, **f32) if self.pad is not None else self.d_weights
+        self._lean = _nat.LeanCalls(module._shape, _nat.Workspace())   # private workspace: pinned for the graphs' lifetime
+        self.plan = None
+        cores = module._cores()
+        state = None if module.optimizer in _SGD_LIKE else module._states()
+        lr, eps = module._lr_arg(), float(module.eps)   # (capturable: the device word, brought up to date; held by address)
+        adam = module._adam_lean()
+        self._adam_key = module._adam_key()
+        ws, cnt, shape = self._lean.ws, self.nnz_dev, module._shape
+        rows_route = self.route == "rows"
+        # the lookup inside the graphs: (ids, bags, destination) forward, (ids, bags, gradient) backward
+        look_offs, look_B = (self.ones, nnz) if rows_route else (self.offsets, B)
+        look_out = self.rows if rows_route else self.output
+        look_grad = self.d_rows if rows_route else (self.d_sums if self.route == "mean" else self.d_output)
+
+        def lookup_forward():
+            if self.exact:
+                _nat.forward_exact(shape, _nat.core_ptrs(cores), self.indices, look_offs, look_B, look_out, ws)
+            else:   # (variable: the route is chosen from the capacities, on the host; the kernels read the live count)
+                self.plan = self._lean.forward(cores, self.indices, look_offs, nnz, look_B, look_out, nnz_dev=cnt)
+
+        def lookup_backward():
+            if self.exact:
+                _nat.backward_exact(shape, _nat.core_ptrs(cores), self.indices, look_offs, look_B, look_grad, ws,
+                                    opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps,
+                                    adam=None if adam is None else (_nat.core_ptrs(adam[0]), adam[1], adam[2]))
+            else:
+                self._lean.backward(cores, state, self.indices, look_offs, nnz, look_B, look_grad, lr, eps, self.plan, adam,
+                                    nnz_dev=cnt)
+
+        def fwd():
+            lookup_forward()
+            if self.route == "mean":
+                _nat.bag_mean(self.output, self.output, self.offsets)
+            elif rows_route and mode == "max":
+                _nat.bag_max(self.rows, self.offsets, self.output, self.argmax, ws, None if self.pad is None else self.indices,
+                             self.pad or 0, nnz_dev=cnt, counted=True)
+            elif rows_route:
+                if self.pad is not None:
+                    _nat.pad_weights(self.indices, self.offsets, self.weights, self.pad, mode == "mean", self.pool_weights,
+                                     nnz_dev=cnt, counted=True)
+                _nat.bag_reduce(self.rows, self.pool_weights, self.offsets, self.output, ws, nnz_dev=cnt, counted=True)
+
+        def bwd():
+            if self.route == "mean":
+                _nat.bag_mean(self.d_output, self.d_sums, self.offsets)
+            elif rows_route and mode == "max":
+                _nat.bag_max_backward(self.d_output, self.argmax, self.offsets, self.d_rows, nnz_dev=cnt, counted=True)
+            elif rows_route:
+                _nat.bag_reduce_backward(self.d_output, self.pool_weights, self.offsets, self.d_rows, ws,
+                                         rows=self.rows if self.weighted else None, d_weights=self.d_weights, nnz_dev=cnt,
+                                         counted=True)
+                if self.weighted and self.pad is not None:
+                    _nat.pad_weights(self.indices, self.offsets, self.d_weights, self.pad, False, self.d_weights_out,
+                                     nnz_dev=cnt, counted=True)
+            lookup_backward()
+
+        # The warm-up runs one backward on a zero gradient outside the capture (workspace growth, LDS-size attributes and size
+        # queries happen there).  That leaves SGD / Adagrad as they are; an Adam step on g = 0 advances t, decays m and v and,
+        # with weight decay, moves the cores: everything is put back, so that a captured module equals an eager one step for step.
+        held = [*cores, *(state or ()), *((*adam[0], module.adam_step) if adam is not None else ())]
+        saved = [t.detach().clone() for t in held]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            fwd()
+            bwd()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        _nat.init()   # the pinned fault word exists before anything is captured (a capture must not allocate it)
+        self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.fwd_graph):
+            fwd()
+        with torch.cuda.graph(self.bwd_graph):
+            bwd()
+        with torch.no_grad():
+            for t, t0 in zip(held, saved):
+                t.copy_(t0)
+        self._lr, self._eps = (None if module.capturable else lr), eps
+        self._baked = self._pointers()
+
+    def __call__(self, indices: torch.Tensor, offsets: Optional[torch.Tensor] = None,
+                 per_sample_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        m, w = self.module, per_sample_weights
+        # every check before anything is launched
+        if m.use_cache and not m.warmup:
+            raise RuntimeError("the row cache went live after capture_bags(): captured bags do not cover a live cache")
+        if m.capturable != (self._lr is None):
+            raise RuntimeError("module.capturable was changed after capture_bags(): capture_bags() again")
+        if m.padding_idx != self.pad or m.mode != self._module_mode:
+            raise RuntimeError("padding_idx / mode of the module are part of the captured graphs: capture_bags() again after "
+                               "changing them")
+        if ((self._lr is not None and float(m.learning_rate) != self._lr) or float(m.eps) != self._eps
+                or m._adam_key() != self._adam_key):
+            raise RuntimeError("learning rate / eps are part of the captured backward: capture_bags() again after changing "
+                               "them (with OptimType.ADAM also betas, weight_decay and decoupled_weight_decay)")
+        if self._pointers() != self._baked:
+            raise RuntimeError("tt_cores / optimizer_state were re-allocated after capture_bags() (.to(), .data = ..., "
+                               "load_state_dict into new storage): capture_bags() again")
+        if (w is not None) != self.weighted:
+            raise ValueError("per_sample_weights given to bags captured with weighted=False: capture_bags(weighted=True) "
+                             "serves them" if w is not None else
+                             "bags captured with weighted=True need per_sample_weights with every call")
+        if self.fanout is not None:
+            if indices.dim() != 2 or indices.shape[1] != self.fanout:
+                raise ValueError(f"bags captured with fanout={self.fanout} take 2-D indices [rows, {self.fanout}], got "
+                                 f"{list(indices.shape)}")
+            if offsets is not None:
+                raise ValueError("offsets has to be None when indices is 2-D (bags of a fixed length)")
+            B_live = indices.shape[0]
+        else:
+            if indices.dim() != 1:
+                raise ValueError(f"indices must be 1-D (2-D calls need capture_bags(fanout=N)), got {list(indices.shape)}")
+            if offsets is None and not self.variable:
+                raise ValueError("offsets is required (bags captured with variable=False and without fanout)")
+            if offsets is not None and offsets.dim() != 1:
+                raise ValueError("offsets must be 1-D")
+            B_live = indices.numel() if offsets is None else offsets.numel() - 1
+        n = indices.numel()
+        if B_live < 0:
+            raise ValueError("offsets must hold B + 1 entries (include_last_offset): got an empty tensor")
+        if w is not None and (w.dtype != torch.float32 or w.shape != indices.shape or w.device != indices.device):
+            raise ValueError(f"per_sample_weights must be float32 of shape {list(indices.shape)} on {indices.device}, got "
+                             f"{w.dtype} {list(w.shape)} on {w.device}")
+        if not indices.is_cuda:
+            raise RuntimeError("TTEmbeddingBag.forward needs tensors on a ROCm device; there is no CPU fallback")
+        if self.variable:
+            if n > self.nnz:
+                raise ValueError(f"{n} ids exceed the captured capacity nnz={self.nnz}: capture_bags() again with a larger one")
+            if B_live > self.B:
+                raise ValueError(f"{B_live} bags exceed the captured capacity B={self.B}: capture_bags() again with a larger one")
+        elif n != self.nnz or B_live != self.B:
+            raise ValueError(f"bags captured with variable=False take exactly nnz={self.nnz} ids in B={self.B} bags, got {n} in "
+                             f"{B_live}")
+        if self._lr is None:
+            m._refresh_lr()   # one fill_ on this stream when learning_rate changed since the last call; no synchronisation
+        ids = indices.reshape(-1)
+        if not ids.is_contiguous():
+            ids = ids.contiguous()
+        flat_w = None
+        if w is not None:
+            flat_w = w.detach().reshape(-1)
+            if not flat_w.is_contiguous():
+                flat_w = flat_w.contiguous()
+        if m.use_cache:   # warm-up: the LFU statistics of a captured step count like those of an eager one
+            m.update_cache(ids if ids.dtype == torch.int64 else ids.long())
+        if self.variable:
+            _nat.stage_bags(ids, offsets, flat_w, self.indices, self.offsets, self.weights, self.nnz_dev,
+                            fanout=self.fanout or 0, B_live=B_live)
+        else:
+            self.indices.copy_(ids)
+            if offsets is not None:
+                self.offsets.copy_(offsets)
+            if flat_w is not None:
+                self.weights.copy_(flat_w)
+        return _ReplayBags.apply(m._cores()[0], self, w, n, B_live)
+
+
 # --------------------------------------------------------------------------------------
 # the module
 # --------------------------------------------------------------------------------------
@@ -1012,6 +1286,14 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         """Lookup whose forward and backward replay captured HIP graphs (see ``CapturedLookup``): of exactly ``nnz`` ids in
         ``B`` bags, or, with ``variable=True``, of any size up to those capacities."""
         return CapturedLookup(self, nnz, B, offsets, variable)
+
+    def capture_bags(self, nnz: int, B: int, *, mode: Optional[str] = None, weighted: bool = False,
+                     fanout: Optional[int] = None, variable: bool = False) -> CapturedBags:
+        """Pooled lookup whose forward and backward replay captured HIP graphs (see ``CapturedBags``): ``mode`` ("sum",
+        "mean", "max"; None = the module's), ``weighted`` (every call brings ``per_sample_weights``), the module's
+        ``padding_idx``, ``fanout=N`` (2-D ``indices[rows, N]``, ``nnz == B * N``) -- of exactly ``nnz`` ids in ``B`` bags, or,
+        with ``variable=True``, of any size up to those capacities."""
+        return CapturedBags(self, nnz, B, mode, weighted, fanout, variable)
 
     # ---- lookup -------------------------------------------------------------------
     def _cores(self) -> tuple:

@@ -936,6 +936,37 @@ __global__ __launch_bounds__(256) void stage_call_kernel(const void* __restrict_
   }
 }
 
+// ttemb_stage_bags: stage_call_kernel for a pooled call.  Element i is also weight i (copied for i < n_live; weights_out
+// past n_live is not touched), and with fanout > 0 the offsets are generated here: i * fanout up to B_live, n_live past it.
+__global__ __launch_bounds__(256) void stage_bags_kernel(const void* __restrict__ indices_in, int ids_i32, long long n_live,
+                                                         const void* __restrict__ offsets_in, int offs_i32, long long B_live,
+                                                         long long fanout, const float* __restrict__ weights_in,
+                                                         int64_t* __restrict__ indices_out, int64_t* __restrict__ offsets_out,
+                                                         long long B_cap, float* __restrict__ weights_out,
+                                                         int32_t* __restrict__ nnz_dev_out) {
+  const long long total = n_live > B_cap + 1 ? n_live : B_cap + 1;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (first == 0) *nnz_dev_out = (int32_t)n_live;
+  for (long long i = first; i < total; i += stride) {
+    if (i < n_live) {
+      indices_out[i] = ids_i32 ? (int64_t) reinterpret_cast<const int32_t*>(indices_in)[i] : reinterpret_cast<const int64_t*>(indices_in)[i];
+      if (weights_in != nullptr) weights_out[i] = weights_in[i];
+    }
+    if (i <= B_cap) {
+      int64_t o = n_live;
+      if (i <= B_live) {
+        if (fanout > 0)
+          o = (int64_t)(i * fanout);
+        else
+          o = offsets_in == nullptr ? (int64_t)i
+                                    : (offs_i32 ? (int64_t) reinterpret_cast<const int32_t*>(offsets_in)[i] : reinterpret_cast<const int64_t*>(offsets_in)[i]);
+      }
+      offsets_out[i] = o;
+    }
+  }
+}
+
 }  // namespace ttemb
 
 using namespace ttemb;
@@ -1445,6 +1476,39 @@ int ttemb_stage_call(const void* indices_in, int32_t indices_are_i32, int64_t n_
                      indices_are_i32 != 0 ? 1 : 0, (long long)n_live, offsets_in, offsets_are_i32 != 0 ? 1 : 0, (long long)B_live, indices_out,
                      offsets_out, (long long)B_cap, nnz_dev_out);
   return check_hip(hipGetLastError(), "stage_call_kernel");
+}
+
+int ttemb_stage_bags(const void* indices_in, int32_t indices_are_i32, int64_t n_live, const void* offsets_in, int32_t offsets_are_i32,
+                     int64_t B_live, int64_t fanout, const float* weights_in, int64_t* indices_out, int64_t nnz_cap,
+                     int64_t* offsets_out, int64_t B_cap, float* weights_out, int32_t* nnz_dev_out, void* stream) {
+  ApiRange api_range("ttemb_stage_bags");
+  if (n_live < 0 || B_live < 0 || nnz_cap < 0 || B_cap < 0) return fail(TTEMB_E_BADARG, "ttemb_stage_bags: negative size");
+  if (fanout < 0) return fail(TTEMB_E_BADARG, "ttemb_stage_bags: negative fanout");
+  if (n_live > nnz_cap)
+    return fail(TTEMB_E_BADARG, "ttemb_stage_bags: %lld ids exceed the capacity of %lld", (long long)n_live, (long long)nnz_cap);
+  if (B_live > B_cap)
+    return fail(TTEMB_E_BADARG, "ttemb_stage_bags: %lld bags exceed the capacity of %lld", (long long)B_live, (long long)B_cap);
+  if (nnz_cap > 0x7fffffffll) return fail(TTEMB_E_BADARG, "ttemb_stage_bags: the id capacity exceeds int32 range (the count word is int32)");
+  if (fanout > 0) {
+    if (offsets_in != nullptr) return fail(TTEMB_E_BADARG, "ttemb_stage_bags: bags of a fixed fanout take no offsets");
+    if (B_live > nnz_cap / fanout || n_live != B_live * fanout)   // (the division first: B_live * fanout cannot overflow)
+      return fail(TTEMB_E_BADARG, "ttemb_stage_bags: %lld ids are not %lld bags of fanout %lld", (long long)n_live, (long long)B_live,
+                  (long long)fanout);
+  } else if (offsets_in == nullptr && B_live != n_live) {
+    return fail(TTEMB_E_BADARG, "ttemb_stage_bags: without offsets every id is a bag of its own, but %lld ids came with %lld bags",
+                (long long)n_live, (long long)B_live);
+  }
+  if ((weights_in == nullptr) != (weights_out == nullptr))
+    return fail(TTEMB_E_BADARG, "ttemb_stage_bags: weights on one side only (weights_in and weights_out go together)");
+  if (offsets_out == nullptr || nnz_dev_out == nullptr || (n_live > 0 && (indices_in == nullptr || indices_out == nullptr)))
+    return fail(TTEMB_E_BADARG, "ttemb_stage_bags: null buffer");
+  const int64_t total = n_live > B_cap + 1 ? n_live : B_cap + 1;
+  int64_t blocks = (total + 255) / 256;
+  blocks = blocks > 2048 ? 2048 : blocks;   // (memory-bound: the grid is capped, the loop strides over the rest)
+  hipLaunchKernelGGL(stage_bags_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), indices_in,
+                     indices_are_i32 != 0 ? 1 : 0, (long long)n_live, offsets_in, offsets_are_i32 != 0 ? 1 : 0, (long long)B_live,
+                     (long long)fanout, weights_in, indices_out, offsets_out, (long long)B_cap, weights_out, nnz_dev_out);
+  return check_hip(hipGetLastError(), "stage_bags_kernel");
 }
 
 int ttemb_adam_step(float* weights, float* exp_avg, float* exp_avg_sq, int32_t* step, const float* grads, int64_t n,

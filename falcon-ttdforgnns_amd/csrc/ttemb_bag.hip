@@ -17,6 +17,12 @@
 // orders set by `offsets` (and D) alone, and every workspace word that is read was written earlier in the same call.
 // Their grids honour ttemb_set_exact_grid.
 //
+// The *_n entry points take a device id count (`nnz_dev`, nullable: the lookups' convention, live_count()): with
+// c = min(nnz, *nnz_dev) every kernel uses c where it would use nnz -- bags are clamped to c, the loops over positions and
+// over chunks stop at c, nothing at a position >= c is read or written -- while the launches and the workspace stay sized by
+// nnz, the capacity.  Chunks are cut from position 0, so the live part is bit for bit what a call with nnz = c gives.  The
+// entry points without the suffix are those calls with nnz_dev = NULL.
+//
 // Lane groups: a group of W lanes (W = the power of two >= D / 4, at most 64) owns one bag / chunk / id and walks its
 // row in float4 columns, W at a time; a workgroup holds kBagNT / W groups.
 #include "ttemb_common.h"
@@ -39,6 +45,8 @@ Groups groups_of(int64_t D4) {
   while ((int64_t(1) << shift) < D4 && shift < 6) ++shift;
   return Groups{shift, kBagNT >> shift};
 }
+
+__host__ __device__ inline int64_t chunks_of(int64_t nnz) { return (nnz + kBagChunk - 1) / kBagChunk; }
 
 __device__ __forceinline__ float4 f4_scale(float w, float4 r) { return make_float4(w * r.x, w * r.y, w * r.z, w * r.w); }
 
@@ -69,9 +77,11 @@ __device__ __forceinline__ float4 weighted_sum(const float4* __restrict__ rows, 
 // chunk's two slots -- slot 0 for the bag that began before the chunk, slot 1 for the bag that begins inside it (a long bag
 // cannot lie wholly inside a chunk, so there are at most these two).  Short bags are summed by bag_reduce_kernel.
 __global__ __launch_bounds__(kBagNT) void bag_partial_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
-                                                             const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
-                                                             int64_t D4, int shift, int64_t nchunks,
-                                                             float4* __restrict__ partial) {
+                                                             const int64_t* __restrict__ offsets, int64_t nnz,
+                                                             const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                             int shift, float4* __restrict__ partial) {
+  nnz = live_count(nnz, nnz_dev);
+  const int64_t nchunks = chunks_of(nnz);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -94,9 +104,11 @@ __global__ __launch_bounds__(kBagNT) void bag_partial_kernel(const float4* __res
 // out[b]: a bag of one id is a scale and a store; a short bag one sum in position order; a long bag the sum of its chunk
 // partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); an empty bag zeros.
 __global__ __launch_bounds__(kBagNT) void bag_reduce_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
-                                                            const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
-                                                            int64_t D4, int shift, const float4* __restrict__ partial,
+                                                            const int64_t* __restrict__ offsets, int64_t nnz,
+                                                            const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                            int shift, const float4* __restrict__ partial,
                                                             float4* __restrict__ out) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -126,8 +138,10 @@ __global__ __launch_bounds__(kBagNT) void bag_reduce_backward_kernel(const float
                                                                      const float* __restrict__ w,
                                                                      const float4* __restrict__ rows,
                                                                      const int64_t* __restrict__ offsets, int64_t nnz,
-                                                                     int64_t B, int64_t D4, int shift,
-                                                                     float4* __restrict__ d_rows, float* __restrict__ d_w) {
+                                                                     const int32_t* __restrict__ nnz_dev, int64_t B,
+                                                                     int64_t D4, int shift, float4* __restrict__ d_rows,
+                                                                     float* __restrict__ d_w) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -179,8 +193,10 @@ __global__ __launch_bounds__(kBagNT) void bag_mean_kernel(const float4* src, flo
 // len' = the kept ids of the bag.  One wavefront per bag (a count by ballots, then the stores); positions outside every bag
 // get 0.  A bag of no kept id gets zeros whatever its weights.
 __global__ __launch_bounds__(kBagNT) void pad_weights_kernel(const int64_t* __restrict__ indices, const int64_t* __restrict__ offsets,
-                                                             const float* __restrict__ w, int64_t nnz, int64_t B, int64_t pad,
+                                                             const float* __restrict__ w, int64_t nnz,
+                                                             const int32_t* __restrict__ nnz_dev, int64_t B, int64_t pad,
                                                              int mean, float* __restrict__ w_out) {
+  nnz = live_count(nnz, nnz_dev);
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t per_block = kBagNT / kWave;
   const int64_t stride = (int64_t)gridDim.x * per_block;
@@ -248,8 +264,10 @@ __device__ __forceinline__ Best4 max_walk(const float4* __restrict__ rows, const
 // partial winners (values in pv, positions in pp; a part of pads only leaves positions of -1).
 __global__ __launch_bounds__(kBagNT) void bag_max_partial_kernel(const float4* __restrict__ rows, const int64_t* __restrict__ indices,
                                                                  int64_t pad, const int64_t* __restrict__ offsets, int64_t nnz,
-                                                                 int64_t B, int64_t D4, int shift, int64_t nchunks,
-                                                                 float4* __restrict__ pv, int4* __restrict__ pp) {
+                                                                 const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                                 int shift, float4* __restrict__ pv, int4* __restrict__ pp) {
+  nnz = live_count(nnz, nnz_dev);
+  const int64_t nchunks = chunks_of(nnz);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -277,10 +295,11 @@ __global__ __launch_bounds__(kBagNT) void bag_max_partial_kernel(const float4* _
 // chunk partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); without a winner
 // (an empty bag, a bag of pads only) zeros and -1.
 __global__ __launch_bounds__(kBagNT) void bag_max_kernel(const float4* __restrict__ rows, const int64_t* __restrict__ indices,
-                                                         int64_t pad, const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
-                                                         int64_t D4, int shift, const float4* __restrict__ pv,
-                                                         const int4* __restrict__ pp, float4* __restrict__ out,
-                                                         int4* __restrict__ argmax) {
+                                                         int64_t pad, const int64_t* __restrict__ offsets, int64_t nnz,
+                                                         const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4, int shift,
+                                                         const float4* __restrict__ pv, const int4* __restrict__ pp,
+                                                         float4* __restrict__ out, int4* __restrict__ argmax) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -307,8 +326,10 @@ __global__ __launch_bounds__(kBagNT) void bag_max_kernel(const float4* __restric
 // d_rows[i][d] = dOut[bag(i)][d] where position i is the winner of (bag(i), d), else 0; every element is written (zeros for
 // a position outside every bag).  One lane group per id.
 __global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* __restrict__ d_out, const int4* __restrict__ argmax,
-                                                                  const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
-                                                                  int64_t D4, int shift, float4* __restrict__ d_rows) {
+                                                                  const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                  const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                                  int shift, float4* __restrict__ d_rows) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -330,8 +351,6 @@ __global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* 
     }
   }
 }
-
-int64_t chunks_of(int64_t nnz) { return (nnz + kBagChunk - 1) / kBagChunk; }
 
 unsigned grid_of(int64_t items, const Groups& gr) { return exact::ex_grid((items + gr.per_block - 1) / gr.per_block); }
 
@@ -357,8 +376,8 @@ int64_t ttemb_bag_workspace_bytes(int64_t nnz, int64_t B, int64_t D) {
   return kBagHeader + 2 * chunks_of(nnz) * D * (int64_t)sizeof(float);
 }
 
-int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, int64_t B, int64_t D,
-                     float* output, void* workspace, int64_t workspace_bytes, void* stream) {
+int ttemb_bag_reduce_n(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
+                       int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes, void* stream) {
   int rc = check_sizes("ttemb_bag_reduce", nnz, B, D);
   if (rc) return rc;
   if (B == 0) return TTEMB_OK;
@@ -376,18 +395,23 @@ int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* off
   float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
   const float4* r4 = reinterpret_cast<const float4*>(rows);
   if (nch > 0) {
-    hipLaunchKernelGGL(bag_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, B, D4,
-                       gr.shift, nch, partial);
+    hipLaunchKernelGGL(bag_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, nnz_dev, B,
+                       D4, gr.shift, partial);
     if ((rc = check_hip(hipGetLastError(), "bag_partial_kernel"))) return rc;
   }
-  hipLaunchKernelGGL(bag_reduce_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, B, D4, gr.shift,
-                     partial, reinterpret_cast<float4*>(output));
+  hipLaunchKernelGGL(bag_reduce_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, nnz_dev, B, D4,
+                     gr.shift, partial, reinterpret_cast<float4*>(output));
   return check_hip(hipGetLastError(), "bag_reduce_kernel");
 }
 
-int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const float* rows, const int64_t* offsets,
-                              int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights, void* workspace,
-                              int64_t workspace_bytes, void* stream) {
+int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, int64_t B, int64_t D,
+                     float* output, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttemb_bag_reduce_n(rows, weights, offsets, nnz, nullptr, B, D, output, workspace, workspace_bytes, stream);
+}
+
+int ttemb_bag_reduce_backward_n(const float* d_output, const float* weights, const float* rows, const int64_t* offsets,
+                                int64_t nnz, const int32_t* nnz_dev, int64_t B, int64_t D, float* d_rows, float* d_weights,
+                                void* workspace, int64_t workspace_bytes, void* stream) {
   (void)workspace;
   (void)workspace_bytes;
   int rc = check_sizes("ttemb_bag_reduce_backward", nnz, B, D);
@@ -404,8 +428,15 @@ int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const
   const Groups gr = groups_of(D4);
   hipLaunchKernelGGL(bag_reduce_backward_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st,
                      reinterpret_cast<const float4*>(d_output), weights, reinterpret_cast<const float4*>(rows), offsets, nnz,
-                     B, D4, gr.shift, reinterpret_cast<float4*>(d_rows), d_weights);
+                     nnz_dev, B, D4, gr.shift, reinterpret_cast<float4*>(d_rows), d_weights);
   return check_hip(hipGetLastError(), "bag_reduce_backward_kernel");
+}
+
+int ttemb_bag_reduce_backward(const float* d_output, const float* weights, const float* rows, const int64_t* offsets,
+                              int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  return ttemb_bag_reduce_backward_n(d_output, weights, rows, offsets, nnz, nullptr, B, D, d_rows, d_weights, workspace,
+                                     workspace_bytes, stream);
 }
 
 int ttemb_bag_mean(const float* src, float* dst, const int64_t* offsets, int64_t B, int64_t D, void* stream) {
@@ -428,8 +459,9 @@ int64_t ttemb_bag_max_workspace_bytes(int64_t nnz, int64_t B, int64_t D) {
   return kBagHeader + 2 * chunks_of(nnz) * D * (int64_t)(sizeof(float) + sizeof(int32_t));
 }
 
-int ttemb_bag_max(const float* rows, const int64_t* indices, int64_t pad, const int64_t* offsets, int64_t nnz, int64_t B,
-                  int64_t D, float* output, int32_t* argmax, void* workspace, int64_t workspace_bytes, void* stream) {
+int ttemb_bag_max_n(const float* rows, const int64_t* indices, int64_t pad, const int64_t* offsets, int64_t nnz,
+                    const int32_t* nnz_dev, int64_t B, int64_t D, float* output, int32_t* argmax, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
   int rc = check_sizes("ttemb_bag_max", nnz, B, D);
   if (rc) return rc;
   if (nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "ttemb_bag_max: nnz = %lld does not fit the int32 positions", (long long)nnz);
@@ -449,17 +481,22 @@ int ttemb_bag_max(const float* rows, const int64_t* indices, int64_t pad, const 
   int4* pp = reinterpret_cast<int4*>(pv + 2 * nch * D4);
   const float4* r4 = reinterpret_cast<const float4*>(rows);
   if (nch > 0) {
-    hipLaunchKernelGGL(bag_max_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz, B, D4,
-                       gr.shift, nch, pv, pp);
+    hipLaunchKernelGGL(bag_max_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz,
+                       nnz_dev, B, D4, gr.shift, pv, pp);
     if ((rc = check_hip(hipGetLastError(), "bag_max_partial_kernel"))) return rc;
   }
-  hipLaunchKernelGGL(bag_max_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz, B, D4, gr.shift,
-                     pv, pp, reinterpret_cast<float4*>(output), reinterpret_cast<int4*>(argmax));
+  hipLaunchKernelGGL(bag_max_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, indices, pad, offsets, nnz, nnz_dev, B, D4,
+                     gr.shift, pv, pp, reinterpret_cast<float4*>(output), reinterpret_cast<int4*>(argmax));
   return check_hip(hipGetLastError(), "bag_max_kernel");
 }
 
-int ttemb_bag_max_backward(const float* d_output, const int32_t* argmax, const int64_t* offsets, int64_t nnz, int64_t B,
-                           int64_t D, float* d_rows, void* stream) {
+int ttemb_bag_max(const float* rows, const int64_t* indices, int64_t pad, const int64_t* offsets, int64_t nnz, int64_t B,
+                  int64_t D, float* output, int32_t* argmax, void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttemb_bag_max_n(rows, indices, pad, offsets, nnz, nullptr, B, D, output, argmax, workspace, workspace_bytes, stream);
+}
+
+int ttemb_bag_max_backward_n(const float* d_output, const int32_t* argmax, const int64_t* offsets, int64_t nnz,
+                             const int32_t* nnz_dev, int64_t B, int64_t D, float* d_rows, void* stream) {
   int rc = check_sizes("ttemb_bag_max_backward", nnz, B, D);
   if (rc) return rc;
   if (nnz > kBagMaxIds)
@@ -473,13 +510,18 @@ int ttemb_bag_max_backward(const float* d_output, const int32_t* argmax, const i
   const int64_t D4 = D / 4;
   const Groups gr = groups_of(D4);
   hipLaunchKernelGGL(bag_max_backward_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st,
-                     reinterpret_cast<const float4*>(d_output), reinterpret_cast<const int4*>(argmax), offsets, nnz, B, D4,
-                     gr.shift, reinterpret_cast<float4*>(d_rows));
+                     reinterpret_cast<const float4*>(d_output), reinterpret_cast<const int4*>(argmax), offsets, nnz, nnz_dev, B,
+                     D4, gr.shift, reinterpret_cast<float4*>(d_rows));
   return check_hip(hipGetLastError(), "bag_max_backward_kernel");
 }
 
-int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,
-                      int64_t pad, int32_t mean, float* weights_out, void* stream) {
+int ttemb_bag_max_backward(const float* d_output, const int32_t* argmax, const int64_t* offsets, int64_t nnz, int64_t B,
+                           int64_t D, float* d_rows, void* stream) {
+  return ttemb_bag_max_backward_n(d_output, argmax, offsets, nnz, nullptr, B, D, d_rows, stream);
+}
+
+int ttemb_pad_weights_n(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz,
+                        const int32_t* nnz_dev, int64_t B, int64_t pad, int32_t mean, float* weights_out, void* stream) {
   if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "ttemb_pad_weights: negative nnz / B");
   if (nnz == 0) return TTEMB_OK;
   if (indices == nullptr || offsets == nullptr || weights_out == nullptr)
@@ -487,8 +529,13 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t per_block = kBagNT / kWave;
   hipLaunchKernelGGL(pad_weights_kernel, dim3(exact::ex_grid((B + per_block - 1) / per_block)), dim3(kBagNT), 0, st, indices,
-                     offsets, weights, nnz, B, pad, mean != 0 ? 1 : 0, weights_out);
+                     offsets, weights, nnz, nnz_dev, B, pad, mean != 0 ? 1 : 0, weights_out);
   return check_hip(hipGetLastError(), "pad_weights_kernel");
+}
+
+int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,
+                      int64_t pad, int32_t mean, float* weights_out, void* stream) {
+  return ttemb_pad_weights_n(indices, offsets, weights, nnz, nullptr, B, pad, mean, weights_out, stream);
 }
 
 }  // extern "C"

@@ -44,6 +44,11 @@ EXPORTED_SYMBOLS = (
     "ttemb_backward_step", "ttemb_backward_step_window", "ttemb_backward_step_exact", "ttemb_flat_step",
 )
 
+# every symbol include/ttemb_bags.h declares (captured pooled lookups; ttemb.h includes that header)
+BAGS_SYMBOLS = ("ttemb_stage_bags", "ttemb_bag_reduce_n", "ttemb_bag_reduce_backward_n", "ttemb_bag_max_n",
+                "ttemb_bag_max_backward_n", "ttemb_pad_weights_n")
+
+
 
 class Shape(ctypes.Structure):
     """Mirror of ``ttemb_shape_t``."""
@@ -197,12 +202,18 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_drop_padding.argtypes = [vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp]
     lib.ttemb_pad_weights.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp]
     lib.ttemb_stage_call.argtypes = [vp, i32, i64, vp, i32, i64, vp, i64, vp, i64, vp, vp]
+    lib.ttemb_stage_bags.argtypes = [vp, i32, i64, vp, i32, i64, i64, vp, vp, i64, vp, i64, vp, vp, vp]
+    lib.ttemb_bag_reduce_n.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_backward_n.argtypes = [vp, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_max_n.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_max_backward_n.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
+    lib.ttemb_pad_weights_n.argtypes = [vp, vp, vp, i64, vp, i64, i64, i32, vp, vp]
     stp = ctypes.POINTER(StepDesc)
     lib.ttemb_backward_step.argtypes = [shp, vp, vp, vp, vp, i64, vp, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_step_window.argtypes = [shp, vp, vp, vp, i64, i64, i64, i64, vp, stp, vp, i64, vp]
     lib.ttemb_backward_step_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_flat_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, stp, vp, vp]
-    for name in EXPORTED_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
                         "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
@@ -732,8 +743,18 @@ def _check_sizes(tensors, n: int) -> None:
             raise ValueError(f"bag pooling: expected float32 with {n} elements, got {t.dtype} {list(t.shape)}")
 
 
-def bag_reduce(rows: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, ws: Workspace) -> None:
-    """``output[b] = sum_{i in bag b} weights[i] rows[i]`` (``ttemb_bag_reduce``): rows [nnz, D], output [B, D] fully written."""
+def _count_word(nnz_dev: Optional[torch.Tensor]) -> Optional[int]:
+    """The device id count of a ``*_n`` pooling call (``counted=True``): an int32 word on the device, or None (NULL: all ids)."""
+    if nnz_dev is not None and (nnz_dev.dtype != torch.int32 or nnz_dev.numel() < 1):
+        raise ValueError("bag pooling: the id count is an int32 word on the device")
+    return _ptr(nnz_dev)
+
+
+def bag_reduce(rows: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, ws: Workspace,
+               nnz_dev: Optional[torch.Tensor] = None, counted: bool = False) -> None:
+    """``output[b] = sum_{i in bag b} weights[i] rows[i]`` (``ttemb_bag_reduce``): rows [nnz, D], output [B, D] fully written.
+    ``counted`` (here and in the pooling calls below): the ``*_n`` entry point, whose kernels stop at the id count in the
+    device word ``nnz_dev`` (None: at nnz)."""
     nnz, D = rows.shape
     B = offsets.numel() - 1
     _check_weights(weights, nnz, rows)
@@ -741,12 +762,17 @@ def bag_reduce(rows: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor,
     dev = output.device
     w = ws.get(bag_workspace_bytes(nnz, B, D), dev)
     with _on_device(dev):
-        _check(LIB.ttemb_bag_reduce(_ptr(rows), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(w), w.numel(),
-                                    _stream(output)))
+        if counted:
+            _check(LIB.ttemb_bag_reduce_n(_ptr(rows), _ptr(weights), _ptr(offsets), nnz, _count_word(nnz_dev), B, D, _ptr(output),
+                                          _ptr(w), w.numel(), _stream(output)))
+        else:
+            _check(LIB.ttemb_bag_reduce(_ptr(rows), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(w), w.numel(),
+                                        _stream(output)))
 
 
 def bag_reduce_backward(d_output: torch.Tensor, weights: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor,
-                        ws: Workspace, rows: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None) -> None:
+                        ws: Workspace, rows: Optional[torch.Tensor] = None, d_weights: Optional[torch.Tensor] = None,
+                        nnz_dev: Optional[torch.Tensor] = None, counted: bool = False) -> None:
     """``d_rows[i] = weights[i] d_output[bag(i)]``, and ``d_weights[i] = <d_output[bag(i)], rows[i]>`` when ``d_weights``
     is given (then ``rows`` is needed); one pass (``ttemb_bag_reduce_backward``)."""
     nnz, D = d_rows.shape
@@ -759,8 +785,13 @@ def bag_reduce_backward(d_output: torch.Tensor, weights: torch.Tensor, offsets: 
     dev = d_rows.device
     w = ws.get(0, dev)
     with _on_device(dev):
-        _check(LIB.ttemb_bag_reduce_backward(_ptr(d_output), _ptr(weights), _ptr(rows), _ptr(offsets), nnz, B, D, _ptr(d_rows),
-                                             _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
+        if counted:
+            _check(LIB.ttemb_bag_reduce_backward_n(_ptr(d_output), _ptr(weights), _ptr(rows), _ptr(offsets), nnz,
+                                                   _count_word(nnz_dev), B, D, _ptr(d_rows), _ptr(d_weights), _ptr(w), w.numel(),
+                                                   _stream(d_rows)))
+        else:
+            _check(LIB.ttemb_bag_reduce_backward(_ptr(d_output), _ptr(weights), _ptr(rows), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                                 _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
 
 
 def bag_mean(src: torch.Tensor, dst: torch.Tensor, offsets: torch.Tensor) -> None:
@@ -784,7 +815,8 @@ def bag_max_workspace_bytes(nnz: int, B: int, D: int) -> int:
 
 
 def bag_max(rows: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, argmax: torch.Tensor, ws: Workspace,
-            indices: Optional[torch.Tensor] = None, pad: int = 0) -> None:
+            indices: Optional[torch.Tensor] = None, pad: int = 0, nnz_dev: Optional[torch.Tensor] = None,
+            counted: bool = False) -> None:
     """``output[b][d] = max_{i in bag b} rows[i][d]``, ``argmax[b][d]`` (int32) the first position that holds it, -1 and zeros
     without one (``ttemb_bag_max``).  With ``indices``, positions whose id equals ``pad`` are skipped."""
     nnz, D = rows.shape
@@ -798,11 +830,16 @@ def bag_max(rows: torch.Tensor, offsets: torch.Tensor, output: torch.Tensor, arg
     dev = output.device
     w = ws.get(bag_max_workspace_bytes(nnz, B, D), dev)
     with _on_device(dev):
-        _check(LIB.ttemb_bag_max(_ptr(rows), _ptr(indices), int(pad), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(argmax),
-                                 _ptr(w), w.numel(), _stream(output)))
+        if counted:
+            _check(LIB.ttemb_bag_max_n(_ptr(rows), _ptr(indices), int(pad), _ptr(offsets), nnz, _count_word(nnz_dev), B, D,
+                                       _ptr(output), _ptr(argmax), _ptr(w), w.numel(), _stream(output)))
+        else:
+            _check(LIB.ttemb_bag_max(_ptr(rows), _ptr(indices), int(pad), _ptr(offsets), nnz, B, D, _ptr(output), _ptr(argmax),
+                                     _ptr(w), w.numel(), _stream(output)))
 
 
-def bag_max_backward(d_output: torch.Tensor, argmax: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor) -> None:
+def bag_max_backward(d_output: torch.Tensor, argmax: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor,
+                     nnz_dev: Optional[torch.Tensor] = None, counted: bool = False) -> None:
     """``d_rows[i][d] = d_output[bag(i)][d]`` where ``argmax[bag(i)][d] == i``, else 0; every element written
     (``ttemb_bag_max_backward``)."""
     nnz, D = d_rows.shape
@@ -812,8 +849,12 @@ def bag_max_backward(d_output: torch.Tensor, argmax: torch.Tensor, offsets: torc
     if argmax.dtype != torch.int32 or argmax.numel() != B * D:
         raise ValueError(f"bag_max_backward: argmax must hold [{B}, {D}] int32")
     with _on_device(d_rows.device):
-        _check(LIB.ttemb_bag_max_backward(_ptr(d_output), _ptr(argmax), _ptr(offsets), nnz, B, D, _ptr(d_rows),
-                                          _stream(d_rows)))
+        if counted:
+            _check(LIB.ttemb_bag_max_backward_n(_ptr(d_output), _ptr(argmax), _ptr(offsets), nnz, _count_word(nnz_dev), B, D,
+                                                _ptr(d_rows), _stream(d_rows)))
+        else:
+            _check(LIB.ttemb_bag_max_backward(_ptr(d_output), _ptr(argmax), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                              _stream(d_rows)))
 
 
 def drop_padding_workspace_bytes(nnz: int, B: int) -> int:
@@ -842,13 +883,17 @@ def drop_padding(indices: torch.Tensor, offsets: torch.Tensor, pad: int, indices
 
 
 def pad_weights(indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor], pad: int, mean: bool,
-                weights_out: torch.Tensor) -> None:
+                weights_out: torch.Tensor, nnz_dev: Optional[torch.Tensor] = None, counted: bool = False) -> None:
     """``weights_out[i] = (indices[i] != pad) * (weights[i] or 1) * (1 / kept ids of its bag if mean)`` (``ttemb_pad_weights``)."""
     nnz = indices.numel()
     _check_sizes((weights, weights_out), nnz)
     with _on_device(weights_out.device):
-        _check(LIB.ttemb_pad_weights(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, offsets.numel() - 1, int(pad),
-                                     1 if mean else 0, _ptr(weights_out), _stream(weights_out)))
+        if counted:
+            _check(LIB.ttemb_pad_weights_n(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, _count_word(nnz_dev),
+                                           offsets.numel() - 1, int(pad), 1 if mean else 0, _ptr(weights_out), _stream(weights_out)))
+        else:
+            _check(LIB.ttemb_pad_weights(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, offsets.numel() - 1, int(pad),
+                                         1 if mean else 0, _ptr(weights_out), _stream(weights_out)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:
@@ -954,6 +999,37 @@ def stage_call(indices: torch.Tensor, offsets: Optional[torch.Tensor], indices_o
                                   1 if offsets is not None and offsets.dtype == torch.int32 else 0, B_live, _ptr(indices_out),
                                   indices_out.numel(), _ptr(offsets_out), offsets_out.numel() - 1, _ptr(nnz_dev_out),
                                   _stream(offsets_out))
+    if rc:
+        _check(rc)
+
+
+def stage_bags(indices: torch.Tensor, offsets: Optional[torch.Tensor], weights: Optional[torch.Tensor],
+               indices_out: torch.Tensor, offsets_out: torch.Tensor, weights_out: Optional[torch.Tensor],
+               nnz_dev_out: torch.Tensor, fanout: int = 0, B_live: Optional[int] = None) -> None:
+    """``stage_call`` for a pooled call, in ONE launch (``ttemb_stage_bags``): also the float32 ``weights`` (``[n]``, or None)
+    into ``weights_out[:n]``, and with ``fanout > 0`` (``n = B_live * fanout`` ids, no ``offsets``) the offsets
+    ``0, fanout, 2 fanout, ...`` generated on the device.  ``weights`` and ``weights_out`` come together."""
+    n = indices.numel()
+    if B_live is None:
+        B_live = n // fanout if fanout > 0 else (n if offsets is None else offsets.numel() - 1)
+    if (indices.dtype not in _ID_DTYPES or (offsets is not None and offsets.dtype not in _ID_DTYPES)
+            or indices_out.dtype != torch.int64 or offsets_out.dtype != torch.int64 or nnz_dev_out.dtype != torch.int32):
+        raise ValueError("stage_bags: ids and offsets must be int64 or int32, the staged buffers int64 and the count word int32")
+    if offsets_out.numel() < 1 or nnz_dev_out.numel() < 1 or (offsets is not None and B_live > offsets.numel() - 1):
+        raise ValueError("stage_bags: offsets_out needs B_cap + 1 entries, nnz_dev_out one int32 and offsets B_live + 1 entries")
+    if (weights is None) != (weights_out is None):
+        raise ValueError("stage_bags: weights and weights_out come together")
+    if weights is not None and (weights.dtype != torch.float32 or weights.numel() != n or weights_out.dtype != torch.float32
+                                or weights_out.numel() < n):
+        raise ValueError(f"stage_bags: weights must be float32 with {n} elements and weights_out float32 with room for them")
+    # (a call without ids brings an empty weight tensor, which has no address: its static buffer is then left out as well)
+    w_in = None if weights is None or n == 0 else _ptr(weights)
+    w_out = None if w_in is None else _ptr(weights_out)
+    with _on_device(offsets_out.device):
+        rc = LIB.ttemb_stage_bags(_ptr(indices), 1 if indices.dtype == torch.int32 else 0, n, _ptr(offsets),
+                                  1 if offsets is not None and offsets.dtype == torch.int32 else 0, B_live, int(fanout), w_in,
+                                  _ptr(indices_out), indices_out.numel(), _ptr(offsets_out), offsets_out.numel() - 1, w_out,
+                                  _ptr(nnz_dev_out), _stream(offsets_out))
     if rc:
         _check(rc)
 

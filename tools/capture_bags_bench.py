@@ -1,0 +1,115 @@
+"""What captured pooled lookups (emb.capture_bags) cost against the eager pooled call, on the products table
+(p = 125.140.140, q = 4.5.5, r = 16.16) with fused SGD: one training step (forward + backward with its update) of a
+fixed-fanout neighbour table with about 29 % pad ids.
+  mean_2048       2 048 destinations x fanout 10, mode="mean" (the SAGE mean over a padded neighbour table)
+  weighted_2048   the same table with per_sample_weights, mode="sum" (the GCN-weighted aggregation)
+  mean_40960      40 960 x 10, mode="mean": the large end
+  mean_2048_nopad / weighted_2048_nopad   the 2 048 x 10 workloads on a table without pad ids and a module without
+                  padding_idx, for orientation: a padded captured call always looks every id up (the masked rows of DESIGN
+                  §4.8, where the one hot pad id serialises the lookup), an unpadded one does not
+Legs of each workload:
+  eager       emb(table[, per_sample_weights=w]).backward(dy)
+  fixed       emb.capture_bags(n, rows, ..., fanout=10): the call of exactly that size
+  var_n       ... variable=True at capacity = size: the staging launch and the device count on top of `fixed`
+  var_2n      ... variable=True at twice the size: launches sized by twice the live size
+One process; the legs alternate (eager, fixed, var_n, var_2n, eager, ...) in blocks of --steps steps, so they see the same
+clocks.  Per block: host_us = time to enqueue the block / steps (no synchronisation inside a block), wall_us = time until the
+device has finished it / steps.  Reported: the median over --rounds blocks.  The first failure ends the run.
+--eager-only times the eager leg alone and needs nothing of capture_bags: copied into a checkout of the parent commit it
+gives that commit's numbers, the baseline, from the same session.  Prints one JSON line; --out writes it as a JSON file."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "falcon-ttdforgnns_amd")]
+
+from FBTT.tt_embeddings_ops import OptimType, TTEmbeddingBag  # noqa: E402
+
+P, Q, R = [125, 140, 140], [4, 5, 5], [16, 16]
+FANOUT = 10
+# (name, destinations, mode, weighted, padded)
+WORKLOADS = (("mean_2048", 2_048, "mean", False, True), ("weighted_2048", 2_048, "sum", True, True),
+             ("mean_40960", 40_960, "mean", False, True), ("mean_2048_nopad", 2_048, "mean", False, False),
+             ("weighted_2048_nopad", 2_048, "sum", True, False))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50, help="steps per block")
+    ap.add_argument("--rounds", type=int, default=9, help="blocks per leg")
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--eager-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows, D = int(np.prod(P)), int(np.prod(Q))
+    pad = rows - 1
+    dev = "cuda"
+    rng = np.random.default_rng(0)
+
+    def module(mode, padded):
+        torch.manual_seed(0)
+        return TTEmbeddingBag(rows, D, R, P, Q, optimizer=OptimType.SGD, learning_rate=1e-6, use_cache=False, weight_dist="normal",
+                              mode=mode, padding_idx=pad if padded else None)
+
+    res = {"device": torch.cuda.get_device_name(0), "steps_per_block": a.steps, "rounds": a.rounds, "fanout": FANOUT,
+           "eager_only": a.eager_only, "workloads": {}}
+    for name, n_dst, mode, weighted, padded in WORKLOADS:
+        nbr = rng.integers(0, rows - 1, size=(n_dst, FANOUT))
+        if padded:
+            deg = rng.integers(1, FANOUT + 1, size=n_dst)   # nodes with fewer neighbours than the fanout are filled with the pad
+            deg[rng.random(n_dst) < 0.35] = FANOUT
+            nbr[np.arange(FANOUT)[None, :] >= deg[:, None]] = pad
+        table = torch.as_tensor(nbr).to(dev)
+        w = torch.rand(n_dst, FANOUT, device=dev) if weighted else None
+        dy = torch.randn(n_dst, D, device=dev) * 1e-3
+        n = n_dst * FANOUT
+        eager = module(mode, padded)
+        legs = {"eager": lambda: eager(table, per_sample_weights=w).backward(dy)}
+        if not a.eager_only:
+            kw = dict(mode=mode, weighted=weighted, fanout=FANOUT)
+            fixed = module(mode, padded).capture_bags(n, n_dst, **kw)
+            var_n = module(mode, padded).capture_bags(n, n_dst, variable=True, **kw)
+            var_2n = module(mode, padded).capture_bags(2 * n, 2 * n_dst, variable=True, **kw)
+            legs["fixed"] = lambda: fixed(table, None, w).backward(dy)
+            legs["var_n"] = lambda: var_n(table, None, w).backward(dy)
+            legs["var_2n"] = lambda: var_2n(table, None, w).backward(dy)
+        for fn in legs.values():
+            for _ in range(a.warmup):
+                fn()
+        torch.cuda.synchronize()
+        host = {k: [] for k in legs}
+        wall = {k: [] for k in legs}
+        for _ in range(a.rounds):
+            for k, fn in legs.items():
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                host[k].append((t1 - t0) / a.steps * 1e6)
+                wall[k].append((t2 - t0) / a.steps * 1e6)
+        med = lambda v: round(float(np.median(v)), 1)
+        out = {"destinations": n_dst, "ids": n, "pad_share": round(float((nbr == pad).mean()), 3), "mode": mode,
+               "weighted": weighted, "eager_pad_route": eager._last_pad_route if padded else None,
+               "wall_us": {k: med(v) for k, v in wall.items()}, "host_us": {k: med(v) for k, v in host.items()}}
+        if not a.eager_only:
+            out["fixed_vs_eager_wall"] = round(float(np.median(wall["fixed"]) / np.median(wall["eager"])), 3)
+            out["var_n_vs_fixed_wall"] = round(float(np.median(wall["var_n"]) / np.median(wall["fixed"])), 3)
+            out["var_2n_vs_var_n_wall"] = round(float(np.median(wall["var_2n"]) / np.median(wall["var_n"])), 3)
+        res["workloads"][name] = out
+        legs.clear()
+    print(json.dumps(res), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
