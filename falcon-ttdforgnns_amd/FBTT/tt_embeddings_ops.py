@@ -68,16 +68,18 @@ class OptimType(Enum):
 _SGD_LIKE = (OptimType.SGD, OptimType.EXACT_SGD)
 
 
-def _step_call(m: "TableBatchedTTEmbeddingBag", table: int = 0):
-    """(state, adam) of a fused backward on table ``table``: ``state`` is None for SGD, the Adagrad state or Adam's first
-    moment; ``adam`` is None or (second moment, the table's device step words, hyper-parameters)."""
+def _step_call(m: "TableBatchedTTEmbeddingBag", table: int = 0) -> "_nat.Step":
+    """The fused step of a backward on table ``table``: the rate (a capturable module: its device word, else the float), eps,
+    ``state`` (None for SGD, the Adagrad state or Adam's first moment) and for Adam the second moment, the table's device
+    step words and the hyper-parameters."""
+    lr, eps = m._lr_arg(), float(m.eps)
     if m.optimizer in _SGD_LIKE:
-        return None, None
+        return _nat.Step(lr, eps)
     state = _nat.core_ptrs(m._states(), table)
     if m.optimizer != OptimType.ADAM:
-        return state, None
+        return _nat.Step(lr, eps, state)
     v, step0, hp = m._adam_lean()
-    return state, (_nat.core_ptrs(v, table), step0 if table == 0 else m.adam_step[table], hp)
+    return _nat.Step(lr, eps, state, (_nat.core_ptrs(v, table), step0 if table == 0 else m.adam_step[table], hp))
 
 
 class BufferList(nn.Module):
@@ -314,22 +316,14 @@ class TTLookupFunction(torch.autograd.Function):
         n_fixed = 9
         cached = ctx.live_cache and nnz > 0
         if m.sparse:
-            state, adam = _step_call(m, table)
-            lr, eps = m._lr_arg(), float(m.eps)   # (a capturable module: its device word, else the float)
-            if adam is not None:   # (never with a live cache: the constructor refuses that combination)
-                _nat.backward_adam(m._shape, cores, state, adam[0], adam[1], indices, rowidx, nnz, nnz_dev, B, d_output,
-                                   adam[2], m._ws, ctx.plan, offsets, lr if m.capturable else None)
-            elif state is None:
-                _nat.backward_sgd(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, m._ws, ctx.plan, offsets)
-                if cached:
-                    _nat.cache_backward_sgd(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, lr, m.cache_weight.data,
-                                            nnz_dev[1:] if nnz_dev.numel() > 1 else None)
-            else:
-                _nat.backward_adagrad(m._shape, cores, state, indices, rowidx, nnz, nnz_dev, B, d_output, lr, eps, m._ws,
-                                      ctx.plan, offsets)
-                if cached:
-                    _nat.cache_backward_rowwise_adagrad(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, lr, eps,
-                                                        m.cache_optimizer_state, m.cache_weight.data)
+            step = _step_call(m, table)
+            _nat.backward_fused(m._shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, step, m._ws, ctx.plan, offsets)
+            if cached and step.state is None:   # (never Adam with a live cache: the constructor refuses that combination)
+                _nat.cache_backward_sgd(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, step.lr, m.cache_weight.data,
+                                        nnz_dev[1:] if nnz_dev.numel() > 1 else None)
+            elif cached:
+                _nat.cache_backward_rowwise_adagrad(cache_loc, rowidx, 0, nnz_dev, nnz, d_output, step.lr, step.eps,
+                                                    m.cache_optimizer_state, m.cache_weight.data)
             return (None,) * (n_fixed + len(m.tt_cores))
         # (for ttemb_dist: did this gradient come from a grouped backward -- the family with bounded device-side waits,
         #  whose last kernel leaves its verdict in the workspace header?  Host-side rule, launches nothing.)
@@ -372,11 +366,10 @@ class _TablesLookup(torch.autograd.Function):
         d_output = _f32(d_output)
         T = m.num_tables
         if m.sparse:
-            lr = m._lr_arg()
             for k in range(T):
-                state, adam = _step_call(m, k)   # (Adam: one step count per table, advanced by that table's window)
+                step = _step_call(m, k)   # (Adam: one step count per table, advanced by that table's window)
                 _nat.backward_window(m._shape, _nat.core_ptrs(m.tt_cores, k), indices, offsets, k * B, B, d_output, m._ws,
-                                     opt_state=state, lr=lr, eps=float(m.eps), adam=adam)
+                                     opt_state=step.state, lr=step.lr, eps=step.eps, adam=step.adam)
             return (None,) * (4 + len(m.tt_cores))
         grads = [torch.empty_like(c) for c in m.tt_cores]
         for k in range(T):
@@ -467,9 +460,9 @@ class _ExactLookup(torch.autograd.Function):
         cores = _nat.core_ptrs(m.tt_cores, table)
         n_fixed = 5
         if m.sparse:
-            state, adam = _step_call(m, table)
-            _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, opt_state=state,
-                                lr=m._lr_arg(), eps=float(m.eps), adam=adam)
+            step = _step_call(m, table)
+            _nat.backward_exact(m._shape, cores, indices, offsets, B, d_output, m._ws, opt_state=step.state, lr=step.lr,
+                                eps=step.eps, adam=step.adam)
             return (None,) * (n_fixed + len(m.tt_cores))
         m._last_bwd_grouped = False   # no bounded device-side waits: nothing in the workspace header to look at
         full = _deliver_dense(m, table, m.num_tables == 1,

@@ -749,27 +749,24 @@ __global__ void fused_step_kernel(Seg3 seg, float lr_arg, const float* __restric
   }
 }
 
-static int run_sgd(float* w, const float* g, int64_t n, float lr, hipStream_t st, const float* skip = nullptr,
-                   const float* lr_dev = nullptr) {
-  if (n <= 0) return TTEMB_OK;
+static int run_sgd(const FusedUpdate& upd, float* w, const float* g, int64_t n, const float* skip, hipStream_t st) {
   if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(g)) & 15)
     return fail(TTEMB_E_BADARG, "sgd_step: buffers must be 16-byte aligned");
   const int threads = 256;
   const int64_t blocks = ((n + 3) / 4 + threads - 1) / threads;
-  hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, g, n, lr, lr_dev, skip);
+  hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, g, n, upd.lr, upd.lr_dev, skip);
   return check_hip(hipGetLastError(), "sgd_step_kernel");
 }
 
-static int run_adagrad(float* w, float* state, const float* g, int64_t n, float lr, float eps, hipStream_t st,
-                       const float* lr_dev = nullptr) {
-  if (n <= 0) return TTEMB_OK;
+static int run_adagrad(const FusedUpdate& upd, float* w, const float* g, int64_t n, hipStream_t st) {
   const int threads = 256;
   const int64_t blocks = (n + threads - 1) / threads;
-  hipLaunchKernelGGL(adagrad_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, state, g, n, lr, lr_dev, eps);
+  hipLaunchKernelGGL(adagrad_step_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, w, upd.st[0], g, n, upd.lr, upd.lr_dev, upd.eps);
   return check_hip(hipGetLastError(), "adagrad_step_kernel");
 }
 
-int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd) {
+// a ttemb_adam_t into the lr, eps and Adam fields of a FusedUpdate; TTEMB_E_BADARG outside torch.optim.Adam's domain
+static int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd) {
   if (hp == nullptr || step == nullptr) return fail(TTEMB_E_BADARG, "adam: null hyper-parameters / step words");
   if (!(hp->beta1 >= 0.0 && hp->beta1 < 1.0) || !(hp->beta2 >= 0.0 && hp->beta2 < 1.0))
     return fail(TTEMB_E_BADARG, "adam: betas (%g, %g) outside [0, 1)", hp->beta1, hp->beta2);
@@ -790,19 +787,65 @@ int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd) {
   return TTEMB_OK;
 }
 
-int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
+int step_arrays(const ttemb_shape_t* shape) { return shape != nullptr && shape->T >= 2 && shape->T <= TTEMB_MAX_CORES ? shape->T : 0; }
+
+int step_from_values(int32_t kind, int T, float lr, float eps, float* const* state, float* const* state2, const ttemb_adam_t* hp,
+                     int32_t* adam_step, FusedUpdate* upd) {
+  memset(upd, 0, sizeof(*upd));
+  const bool adam = kind == TTEMB_STEP_ADAM, adagrad = kind == TTEMB_STEP_ADAGRAD;
+  if (adam) {
+    if (state == nullptr || state2 == nullptr) return fail(TTEMB_E_BADARG, "exp_avg / exp_avg_sq is null");
+    int rc = adam_fill(hp, adam_step, upd);
+    if (rc) return rc;
+  } else {
+    if (adagrad && state == nullptr) return fail(TTEMB_E_BADARG, "opt_state is null");
+    upd->lr = lr;
+    upd->eps = adagrad ? eps : 0.f;
+  }
+  for (int t = 0; t < T && (adam || adagrad); ++t) {   // (the kind is read off st[0] / v[0] from here on: no null among them)
+    if (state[t] == nullptr || (adam && state2[t] == nullptr)) return fail(TTEMB_E_BADARG, "null buffer");
+    upd->st[t] = state[t];
+    upd->v[t] = adam ? state2[t] : nullptr;
+  }
+  return TTEMB_OK;
+}
+
+int step_from_descriptor(const ttemb_step_t* step, int T, const FlatArrays* flat, FusedUpdate* upd) {
+  if (step == nullptr) return fail(TTEMB_E_BADARG, "step: null descriptor");
+  if (step->kind != TTEMB_STEP_SGD && step->kind != TTEMB_STEP_ADAGRAD && step->kind != TTEMB_STEP_ADAM)
+    return fail(TTEMB_E_BADARG, "step: kind %d is none of TTEMB_STEP_SGD / _ADAGRAD / _ADAM", (int)step->kind);
+  if (step->lr_dev == nullptr) return fail(TTEMB_E_BADARG, "step: lr_dev is null (the by-value calls take the rate on the host)");
+  if (reinterpret_cast<uintptr_t>(step->lr_dev) & 15) return fail(TTEMB_E_BADARG, "step: lr_dev must be 16-byte aligned");
+  float* const* state = flat != nullptr ? &flat->state : step->state;
+  float* const* state2 = flat != nullptr ? &flat->state2 : step->state2;
+  if (step->kind == TTEMB_STEP_ADAGRAD && state == nullptr) return fail(TTEMB_E_BADARG, "step: state is null (Adagrad)");
+  ttemb_adam_t hp = {};   // (the descriptor's hyper-parameters with their lr ignored: 0 stands in for it, every kernel reads the word)
+  if (step->kind == TTEMB_STEP_ADAM) {
+    if (state == nullptr || state2 == nullptr) return fail(TTEMB_E_BADARG, "step: state / state2 is null (Adam's moments)");
+    if (step->adam == nullptr) return fail(TTEMB_E_BADARG, "step: adam is null (the hyper-parameters)");
+    hp = *step->adam;
+    hp.lr = 0.f;
+  }
+  int rc = step_from_values(step->kind, T, 0.f, step->eps, state, state2, &hp, flat != nullptr ? flat->adam_step : step->adam_step, upd);
+  if (rc) return rc;
+  upd->lr_dev = step->lr_dev;
+  return TTEMB_OK;
+}
+
+int run_step_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
                     hipStream_t st) {
+  const bool adam = upd.v[0] != nullptr, adagrad = !adam && upd.st[0] != nullptr;
   Seg3 seg;
   AdamSeg ad;
   memset(&seg, 0, sizeof(seg));
   memset(&ad, 0, sizeof(ad));
   long long nmax = 0;
   for (int t = 0; t < T; ++t) {
-    if (n[t] > 0 && (upd.w[t] == nullptr || upd.st[t] == nullptr || upd.v[t] == nullptr || g[t] == nullptr))
-      return fail(TTEMB_E_BADARG, "adam: null buffer");
+    if (n[t] > 0 && (upd.w[t] == nullptr || g[t] == nullptr || ((adam || adagrad) && upd.st[t] == nullptr) || (adam && upd.v[t] == nullptr)))
+      return fail(TTEMB_E_BADARG, "step: null buffer");
     if ((reinterpret_cast<uintptr_t>(upd.w[t]) | reinterpret_cast<uintptr_t>(upd.st[t]) | reinterpret_cast<uintptr_t>(upd.v[t]) |
          reinterpret_cast<uintptr_t>(g[t])) & 15)
-      return fail(TTEMB_E_BADARG, "adam: weights, moments and gradients must be 16-byte aligned");
+      return fail(TTEMB_E_BADARG, "step: weights, optimizer state and gradients must be 16-byte aligned");
     seg.w[t] = upd.w[t];
     seg.st[t] = upd.st[t];
     seg.g[t] = g[t];
@@ -810,19 +853,22 @@ int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long lo
     ad.v[t] = upd.v[t];
     nmax = n[t] > nmax ? n[t] : nmax;
   }
-  if (nmax == 0 || ad.v[0] == nullptr) return TTEMB_OK;
-  ad.step = upd.step;
-  ad.b1 = upd.b1; ad.omb1 = upd.omb1; ad.b2 = upd.b2; ad.omb2 = upd.omb2;
-  ad.wd = upd.wd;
-  ad.grad_scale = grad_scale;
-  ad.decoupled = upd.decoupled;
-  hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, st, adam_prep_of(upd));
-  int rc = check_hip(hipGetLastError(), "adam_prepare_kernel");
-  if (rc) return rc;
+  if (nmax == 0) return TTEMB_OK;
+  if (adam) {
+    ad.step = upd.step;
+    ad.b1 = upd.b1; ad.omb1 = upd.omb1; ad.b2 = upd.b2; ad.omb2 = upd.omb2;
+    ad.wd = upd.wd;
+    ad.grad_scale = grad_scale;
+    ad.decoupled = upd.decoupled;
+    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, st, adam_prep_of(upd));
+    int rc = check_hip(hipGetLastError(), "adam_prepare_kernel");
+    if (rc) return rc;
+  }
   long long blocks = (nmax / 4 + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
-  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)T), dim3(256), 0, st, seg, upd.lr, upd.lr_dev, upd.eps, 0, skip, ad);
-  return check_hip(hipGetLastError(), "fused_step_kernel (adam)");
+  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)T), dim3(256), 0, st, seg, upd.lr, upd.lr_dev, upd.eps,
+                     adagrad ? 1 : 0, skip, ad);
+  return check_hip(hipGetLastError(), "fused_step_kernel");
 }
 
 static int check_lookup_args(const void* cores, const void* indices, int64_t nnz, int64_t B) {
@@ -1220,12 +1266,11 @@ int ttemb_backward_dense(const ttemb_shape_t* shape, const float* const* cores,
   return backward_into(r, e.ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, dp, ws, rest, plan, plan_bytes, e.st, e.header);
 }
 
-static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state,
-                          const int64_t* indices, const int64_t* rowidx, const int64_t* offsets, int64_t nnz,
-                          const int32_t* nnz_dev, int64_t B, const float* d_output, float lr, float eps,
-                          void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
-                          void* stream, const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr,
-                          const float* lr_dev = nullptr) {
+// body of the fused-step backward entry points.  `step`: the description a builder filled (every field but w)
+static int fused_backward(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* rowidx,
+                          const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, const float* d_output,
+                          const FusedUpdate& step, void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
+                          void* stream) {
   Entry e;
   int rc = enter(shape, cores, indices, nnz, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
@@ -1237,10 +1282,13 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   if (workspace == nullptr || workspace_bytes < need)
     return fail(TTEMB_E_WORKSPACE, "backward needs %lld workspace bytes, got %lld", (long long)need, (long long)workspace_bytes);
   CorePtrsMut gp;   // the gradient scratch behind the header
+  const float* g[TTEMB_MAX_CORES];
+  long long n[TTEMB_MAX_CORES];
   int64_t off = 0;
   for (int t = 0; t < TTEMB_MAX_CORES; ++t) {
-    gp.c[t] = t < ds.T ? reinterpret_cast<float*>(e.ws + off) : nullptr;
-    if (t < ds.T) off += align256((int64_t)ds.p[t] * ds.row_len[t] * 4);
+    g[t] = gp.c[t] = t < ds.T ? reinterpret_cast<float*>(e.ws + off) : nullptr;
+    n[t] = t < ds.T ? (long long)ds.p[t] * ds.row_len[t] : 0;
+    off += align256(n[t] * 4);
   }
   char* rest_ws = e.ws + off;
   int64_t rest = e.ws_bytes - off;
@@ -1249,57 +1297,16 @@ static int fused_backward(const ttemb_shape_t* shape, float* const* cores, float
   const Route r = route_of(ds, nnz, B, offsets != nullptr, rowidx == nullptr && offsets != nullptr);
   // the grouped path of a one-piece call applies the step inside its last kernel; every other route writes gradients, then steps
   const bool fused = r.kind == kGrouped && fast3_fits(ds, nnz, B);
-  bool aligned4 = true;
-  FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  if (adam != nullptr) upd = *adam;   // (lr, eps, the step words and the Adam hyper-parameters: adam_fill)
-  for (int t = 0; t < ds.T; ++t) {
-    upd.w[t] = cores[t];
-    upd.st[t] = opt_state ? opt_state[t] : nullptr;
-    upd.v[t] = adam != nullptr ? exp_avg_sq[t] : nullptr;
-    aligned4 = aligned4 && cores[t] != nullptr && (!opt_state || opt_state[t] != nullptr) && (adam == nullptr || exp_avg_sq[t] != nullptr);
-  }
-  if (!aligned4) return fail(TTEMB_E_BADARG, "null core / optimizer state");
-  if (adam == nullptr) {
-    upd.lr = lr;
-    upd.eps = eps;
-  }
-  upd.lr_dev = lr_dev;
+  FusedUpdate upd = step;
+  for (int t = 0; t < ds.T; ++t)
+    if ((upd.w[t] = cores[t]) == nullptr) return fail(TTEMB_E_BADARG, "null core / optimizer state");
   rc = backward_into(r, ds, e.cp, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, gp, rest_ws, rest, plan, plan_bytes, e.st,
                      e.header, fused ? &upd : nullptr);
   if (rc || fused) return rc;
+  // (a grouped backward left its verdict in the header's poison word: a poisoned plan leaves the parameters alone)
   const uint32_t* header_skip =
       r.grouped ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(e.header) + kHeaderPoisonOffset) : nullptr;
-  if (adam != nullptr) {   // the Adam step of every core from the gradient scratch: a prepare launch and the step launch
-    const float* g[TTEMB_MAX_CORES];
-    long long n[TTEMB_MAX_CORES];
-    for (int t = 0; t < ds.T; ++t) {
-      g[t] = gp.c[t];
-      n[t] = (long long)ds.p[t] * ds.row_len[t];
-    }
-    return run_adam_arrays(upd, g, n, ds.T, 1.f, header_skip, e.st);
-  }
-  Seg3 seg;
-  memset(&seg, 0, sizeof(seg));
-  int64_t nmax = 0;
-  bool aligned = true;
-  for (int t = 0; t < ds.T; ++t) {
-    seg.w[t] = cores[t];
-    seg.st[t] = opt_state ? opt_state[t] : nullptr;
-    seg.g[t] = gp.c[t];
-    seg.n[t] = (long long)ds.p[t] * ds.row_len[t];
-    nmax = seg.n[t] > nmax ? seg.n[t] : nmax;
-    aligned = aligned && ((reinterpret_cast<uintptr_t>(cores[t]) | (opt_state ? reinterpret_cast<uintptr_t>(opt_state[t]) : 0)) & 15) == 0;
-  }
-  if (!aligned) return fail(TTEMB_E_BADARG, "cores / optimizer state must be 16-byte aligned");
-  int64_t blocks = (nmax / 4 + 255) / 256;
-  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
-  // (a grouped backward left its verdict in the header's poison word: a poisoned plan leaves the parameters alone)
-  AdamSeg no_adam;
-  memset(&no_adam, 0, sizeof(no_adam));
-  hipLaunchKernelGGL(fused_step_kernel, dim3((unsigned)blocks, (unsigned)ds.T), dim3(256), 0, e.st, seg, lr, lr_dev, eps,
-                     opt_state ? 1 : 0, header_skip, no_adam);
-  return check_hip(hipGetLastError(), "fused_step_kernel");
+  return run_step_arrays(upd, g, n, ds.T, 1.f, header_skip, e.st);
 }
 
 int ttemb_backward_adam(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
@@ -1307,13 +1314,11 @@ int ttemb_backward_adam(const ttemb_shape_t* shape, float* const* cores, float* 
                         const int32_t* nnz_dev, int64_t B, const float* d_output, const ttemb_adam_t* hp,
                         void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_adam");
-  if (exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exp_avg / exp_avg_sq is null");
-  FusedUpdate adam;
-  memset(&adam, 0, sizeof(adam));
-  int rc = adam_fill(hp, step, &adam);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAM, step_arrays(shape), 0.f, 0.f, exp_avg, exp_avg_sq, hp, step, &upd);
   if (rc) return rc;
-  return fused_backward(shape, cores, exp_avg, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, hp->lr, hp->eps, workspace,
-                        workspace_bytes, plan, plan_bytes, stream, &adam, exp_avg_sq);
+  return fused_backward(shape, cores, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, upd, workspace, workspace_bytes, plan,
+                        plan_bytes, stream);
 }
 
 int ttemb_backward_sgd(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices,
@@ -1321,8 +1326,11 @@ int ttemb_backward_sgd(const ttemb_shape_t* shape, float* const* cores, const in
                        const float* d_output, float lr, void* workspace, int64_t workspace_bytes,
                        const void* plan, int64_t plan_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_sgd");
-  return fused_backward(shape, cores, nullptr, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, lr, 0.f,
-                        workspace, workspace_bytes, plan, plan_bytes, stream);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_SGD, step_arrays(shape), lr, 0.f, nullptr, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return fused_backward(shape, cores, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, upd, workspace, workspace_bytes, plan,
+                        plan_bytes, stream);
 }
 
 int ttemb_backward_adagrad(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state,
@@ -1331,9 +1339,11 @@ int ttemb_backward_adagrad(const ttemb_shape_t* shape, float* const* cores, floa
                            float eps, void* workspace, int64_t workspace_bytes, const void* plan,
                            int64_t plan_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_adagrad");
-  if (opt_state == nullptr) return fail(TTEMB_E_BADARG, "opt_state is null");
-  return fused_backward(shape, cores, opt_state, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, lr, eps,
-                        workspace, workspace_bytes, plan, plan_bytes, stream);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAGRAD, step_arrays(shape), lr, eps, opt_state, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return fused_backward(shape, cores, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, upd, workspace, workspace_bytes, plan,
+                        plan_bytes, stream);
 }
 
 // ---- a window of a longer id list: one table of a table-batched call (include/ttemb.h) ----
@@ -1375,17 +1385,17 @@ int ttemb_forward_window(const ttemb_shape_t* shape, const float* const* cores, 
   return launch_forward_window_fast3(e.ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, output, e.ws, e.ws_bytes, e.st, e.header);
 }
 
-static int backward_window(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, float* const* d_cores,
-                           const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B,
-                           const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream,
-                           const FusedUpdate* adam = nullptr, float* const* exp_avg_sq = nullptr, const float* lr_dev = nullptr) {
+// body of the window backward entry points.  `step`: null for dense gradients into `d_cores`, else the description a builder filled
+static int backward_window(const ttemb_shape_t* shape, float* const* cores, float* const* d_cores, const int64_t* indices,
+                           const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, const float* d_output,
+                           const FusedUpdate* step, void* workspace, int64_t workspace_bytes, void* stream) {
   Entry e;
   int rc = window_args(shape, cores, indices, offsets, nnz, bags_total, bag0, B, workspace, workspace_bytes, stream, &e);
   if (rc) return rc;
   const DevShape& ds = e.ds;
   CorePtrsMut dp;
-  for (int t = 0; t < TTEMB_MAX_CORES; ++t) dp.c[t] = (d_cores != nullptr && t < ds.T) ? d_cores[t] : nullptr;
-  if (d_cores != nullptr) {   // dense: every gradient is written whole
+  for (int t = 0; t < TTEMB_MAX_CORES; ++t) dp.c[t] = (step == nullptr && t < ds.T) ? d_cores[t] : nullptr;
+  if (step == nullptr) {   // dense: every gradient is written whole
     for (int t = 0; t < ds.T; ++t)
       if (d_cores[t] == nullptr) return fail(TTEMB_E_BADARG, "d_cores[%d] is null", t);
     if (nnz == 0 || B == 0) return launch_zero_cores(ds, dp, e.st);
@@ -1394,24 +1404,13 @@ static int backward_window(const ttemb_shape_t* shape, float* const* cores, floa
   }
   if (d_output == nullptr) return fail(TTEMB_E_BADARG, "d_output is null");
   FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  if (d_cores == nullptr) {
-    if (adam != nullptr) upd = *adam;   // (lr, eps, the step words and the Adam hyper-parameters: adam_fill)
-    for (int t = 0; t < ds.T; ++t) {
-      upd.w[t] = cores[t];
-      upd.st[t] = opt_state ? opt_state[t] : nullptr;
-      upd.v[t] = adam != nullptr ? exp_avg_sq[t] : nullptr;
-      if (cores[t] == nullptr || (opt_state && opt_state[t] == nullptr) || (adam != nullptr && exp_avg_sq[t] == nullptr))
-        return fail(TTEMB_E_BADARG, "null core / optimizer state");
-    }
-    if (adam == nullptr) {
-      upd.lr = lr;
-      upd.eps = eps;
-    }
-    upd.lr_dev = lr_dev;
+  if (step != nullptr) {
+    upd = *step;
+    for (int t = 0; t < ds.T; ++t)
+      if ((upd.w[t] = cores[t]) == nullptr) return fail(TTEMB_E_BADARG, "null core / optimizer state");
   }
   return launch_backward_window_fast3(ds, e.cp, indices, offsets, nnz, bags_total, bag0, B, d_output, dp, e.ws, e.ws_bytes, e.st,
-                                      d_cores == nullptr ? &upd : nullptr, e.header);
+                                      step != nullptr ? &upd : nullptr, e.header);
 }
 
 int ttemb_backward_dense_window(const ttemb_shape_t* shape, const float* const* cores, const int64_t* indices, const int64_t* offsets,
@@ -1419,7 +1418,7 @@ int ttemb_backward_dense_window(const ttemb_shape_t* shape, const float* const* 
                                 void* workspace, int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_dense_window");
   if (d_cores == nullptr) return fail(TTEMB_E_BADARG, "d_cores is null");
-  return backward_window(shape, const_cast<float* const*>(cores), nullptr, d_cores, indices, offsets, nnz, bags_total, bag0, B, d_output, 0.f, 0.f,
+  return backward_window(shape, const_cast<float* const*>(cores), d_cores, indices, offsets, nnz, bags_total, bag0, B, d_output, nullptr,
                          workspace, workspace_bytes, stream);
 }
 
@@ -1427,17 +1426,22 @@ int ttemb_backward_sgd_window(const ttemb_shape_t* shape, float* const* cores, c
                               int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, const float* d_output, float lr,
                               void* workspace, int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_sgd_window");
-  return backward_window(shape, cores, nullptr, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, lr, 0.f, workspace,
-                         workspace_bytes, stream);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_SGD, step_arrays(shape), lr, 0.f, nullptr, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return backward_window(shape, cores, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, &upd, workspace, workspace_bytes,
+                         stream);
 }
 
 int ttemb_backward_adagrad_window(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, const int64_t* indices,
                                   const int64_t* offsets, int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B,
                                   const float* d_output, float lr, float eps, void* workspace, int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_adagrad_window");
-  if (opt_state == nullptr) return fail(TTEMB_E_BADARG, "opt_state is null");
-  return backward_window(shape, cores, opt_state, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, lr, eps, workspace,
-                         workspace_bytes, stream);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAGRAD, step_arrays(shape), lr, eps, opt_state, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return backward_window(shape, cores, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, &upd, workspace, workspace_bytes,
+                         stream);
 }
 
 int ttemb_backward_adam_window(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
@@ -1445,13 +1449,11 @@ int ttemb_backward_adam_window(const ttemb_shape_t* shape, float* const* cores, 
                                int64_t bag0, int64_t B, const float* d_output, const ttemb_adam_t* hp, void* workspace,
                                int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_adam_window");
-  if (exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exp_avg / exp_avg_sq is null");
-  FusedUpdate adam;
-  memset(&adam, 0, sizeof(adam));
-  int rc = adam_fill(hp, step, &adam);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAM, step_arrays(shape), 0.f, 0.f, exp_avg, exp_avg_sq, hp, step, &upd);
   if (rc) return rc;
-  return backward_window(shape, cores, exp_avg, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, hp->lr, hp->eps, workspace,
-                         workspace_bytes, stream, &adam, exp_avg_sq);
+  return backward_window(shape, cores, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, &upd, workspace, workspace_bytes,
+                         stream);
 }
 
 int ttemb_stage_call(const void* indices_in, int32_t indices_are_i32, int64_t n_live, const void* offsets_in, int32_t offsets_are_i32,
@@ -1511,114 +1513,93 @@ int ttemb_stage_bags(const void* indices_in, int32_t indices_are_i32, int64_t n_
   return check_hip(hipGetLastError(), "stage_bags_kernel");
 }
 
+// body of the flat steps: `n` floats of one array.  sgd_step_kernel / adagrad_step_kernel for SGD / Adagrad (no gradient
+// scale; Adagrad has no skip word), the array step for Adam
+static int flat_step(const FusedUpdate& step, float* weights, const float* grads, int64_t n, float grad_scale, const float* skip,
+                     void* stream) {
+  if (n <= 0) return TTEMB_OK;
+  if (weights == nullptr || grads == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (step.v[0] != nullptr) {
+    FusedUpdate upd = step;
+    upd.w[0] = weights;
+    const long long nn = n;
+    return run_step_arrays(upd, &grads, &nn, 1, grad_scale, reinterpret_cast<const uint32_t*>(skip), st);
+  }
+  if (grad_scale != 1.f) return fail(TTEMB_E_BADARG, "flat step: grad_scale is Adam's (pass 1 for SGD / Adagrad)");
+  if (step.st[0] == nullptr) return run_sgd(step, weights, grads, n, skip, st);
+  if (skip != nullptr) return fail(TTEMB_E_BADARG, "flat step: the Adagrad step takes no skip word");
+  return run_adagrad(step, weights, grads, n, st);
+}
+
 int ttemb_adam_step(float* weights, float* exp_avg, float* exp_avg_sq, int32_t* step, const float* grads, int64_t n,
                     float grad_scale, const ttemb_adam_t* hp, const float* skip, void* stream) {
   ApiRange api_range("ttemb_adam_step");
   if (n < 0) return fail(TTEMB_E_BADARG, "negative n");
   FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  int rc = adam_fill(hp, step, &upd);
-  if (rc || n == 0) return rc;
-  upd.w[0] = weights;
-  upd.st[0] = exp_avg;
-  upd.v[0] = exp_avg_sq;
-  if (weights == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr || grads == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
-  const long long nn = n;
-  return run_adam_arrays(upd, &grads, &nn, 1, grad_scale, reinterpret_cast<const uint32_t*>(skip), reinterpret_cast<hipStream_t>(stream));
+  int rc = step_from_values(TTEMB_STEP_ADAM, n > 0 ? 1 : 0, 0.f, 0.f, &exp_avg, &exp_avg_sq, hp, step, &upd);
+  if (rc) return rc;
+  return flat_step(upd, weights, grads, n, grad_scale, skip, stream);
 }
 
 int ttemb_sgd_step(float* weights, const float* grads, int64_t n, float lr, void* stream) {
   ApiRange api_range("ttemb_sgd_step");
-  if (n > 0 && (weights == nullptr || grads == nullptr)) return fail(TTEMB_E_BADARG, "null buffer");
-  return run_sgd(weights, grads, n, lr, reinterpret_cast<hipStream_t>(stream));
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_SGD, n > 0 ? 1 : 0, lr, 0.f, nullptr, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return flat_step(upd, weights, grads, n, 1.f, nullptr, stream);
 }
 
 int ttemb_sgd_step_guarded(float* weights, const float* grads, int64_t n, float lr, const float* skip, void* stream) {
   ApiRange api_range("ttemb_sgd_step_guarded");
-  if (n > 0 && (weights == nullptr || grads == nullptr)) return fail(TTEMB_E_BADARG, "null buffer");
-  return run_sgd(weights, grads, n, lr, reinterpret_cast<hipStream_t>(stream), skip);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_SGD, n > 0 ? 1 : 0, lr, 0.f, nullptr, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return flat_step(upd, weights, grads, n, 1.f, skip, stream);
 }
 
 int ttemb_adagrad_step(float* weights, float* state, const float* grads, int64_t n, float lr,
                        float eps, void* stream) {
   ApiRange api_range("ttemb_adagrad_step");
-  if (n > 0 && (weights == nullptr || grads == nullptr || state == nullptr)) return fail(TTEMB_E_BADARG, "null buffer");
-  return run_adagrad(weights, state, grads, n, lr, eps, reinterpret_cast<hipStream_t>(stream));
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAGRAD, n > 0 ? 1 : 0, lr, eps, &state, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return flat_step(upd, weights, grads, n, 1.f, nullptr, stream);
 }
 
 // ---- the step of a capturable caller: the learning rate is a device word (include/ttemb.h "Device-resident learning rate") ----
-// what every ttemb_*_step* call starts with: a descriptor the kernels can take.  `flat`: the state pointers are the call's own
-// arguments, the descriptor's are not looked at.  Fills `adam` for TTEMB_STEP_ADAM (the descriptor's hyper-parameters with
-// their lr ignored: 0 stands in for it, every kernel reads the word).
-static int step_args(const ttemb_step_t* step, int32_t* adam_step, bool flat, FusedUpdate* adam) {
-  if (step == nullptr) return fail(TTEMB_E_BADARG, "step: null descriptor");
-  if (step->kind != TTEMB_STEP_SGD && step->kind != TTEMB_STEP_ADAGRAD && step->kind != TTEMB_STEP_ADAM)
-    return fail(TTEMB_E_BADARG, "step: kind %d is none of TTEMB_STEP_SGD / _ADAGRAD / _ADAM", (int)step->kind);
-  if (step->lr_dev == nullptr) return fail(TTEMB_E_BADARG, "step: lr_dev is null (the by-value calls take the rate on the host)");
-  if (reinterpret_cast<uintptr_t>(step->lr_dev) & 15) return fail(TTEMB_E_BADARG, "step: lr_dev must be 16-byte aligned");
-  if (step->kind == TTEMB_STEP_ADAGRAD && !flat && step->state == nullptr) return fail(TTEMB_E_BADARG, "step: state is null (Adagrad)");
-  if (step->kind != TTEMB_STEP_ADAM) return TTEMB_OK;
-  if (!flat && (step->state == nullptr || step->state2 == nullptr)) return fail(TTEMB_E_BADARG, "step: state / state2 is null (Adam's moments)");
-  if (step->adam == nullptr) return fail(TTEMB_E_BADARG, "step: adam is null (the hyper-parameters)");
-  ttemb_adam_t hp = *step->adam;
-  hp.lr = 0.f;
-  memset(adam, 0, sizeof(*adam));
-  int rc = adam_fill(&hp, adam_step, adam);
-  if (rc) return rc;
-  adam->lr_dev = step->lr_dev;
-  return TTEMB_OK;
-}
-
 int ttemb_backward_step(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* rowidx,
                         const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, const float* d_output,
                         const ttemb_step_t* step, void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes,
                         void* stream) {
   ApiRange api_range("ttemb_backward_step");
-  FusedUpdate adam;
-  int rc = step_args(step, step != nullptr ? step->adam_step : nullptr, false, &adam);
+  FusedUpdate upd;
+  int rc = step_from_descriptor(step, step_arrays(shape), nullptr, &upd);
   if (rc) return rc;
-  const bool is_adam = step->kind == TTEMB_STEP_ADAM;
-  return fused_backward(shape, cores, step->kind == TTEMB_STEP_SGD ? nullptr : step->state, indices, rowidx, offsets, nnz, nnz_dev, B,
-                        d_output, 0.f, step->kind == TTEMB_STEP_ADAGRAD ? step->eps : 0.f, workspace, workspace_bytes, plan, plan_bytes,
-                        stream, is_adam ? &adam : nullptr, is_adam ? step->state2 : nullptr, step->lr_dev);
+  return fused_backward(shape, cores, indices, rowidx, offsets, nnz, nnz_dev, B, d_output, upd, workspace, workspace_bytes, plan,
+                        plan_bytes, stream);
 }
 
 int ttemb_backward_step_window(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets,
                                int64_t nnz, int64_t bags_total, int64_t bag0, int64_t B, const float* d_output,
                                const ttemb_step_t* step, void* workspace, int64_t workspace_bytes, void* stream) {
   ApiRange api_range("ttemb_backward_step_window");
-  FusedUpdate adam;
-  int rc = step_args(step, step != nullptr ? step->adam_step : nullptr, false, &adam);
+  FusedUpdate upd;
+  int rc = step_from_descriptor(step, step_arrays(shape), nullptr, &upd);
   if (rc) return rc;
-  const bool is_adam = step->kind == TTEMB_STEP_ADAM;
-  return backward_window(shape, cores, step->kind == TTEMB_STEP_SGD ? nullptr : step->state, nullptr, indices, offsets, nnz, bags_total,
-                         bag0, B, d_output, 0.f, step->kind == TTEMB_STEP_ADAGRAD ? step->eps : 0.f, workspace, workspace_bytes, stream,
-                         is_adam ? &adam : nullptr, is_adam ? step->state2 : nullptr, step->lr_dev);
+  return backward_window(shape, cores, nullptr, indices, offsets, nnz, bags_total, bag0, B, d_output, &upd, workspace, workspace_bytes,
+                         stream);
 }
 
 int ttemb_flat_step(float* weights, float* state, float* state2, int32_t* adam_step, const float* grads, int64_t n, float grad_scale,
                     const ttemb_step_t* step, const float* skip, void* stream) {
   ApiRange api_range("ttemb_flat_step");
   if (n < 0) return fail(TTEMB_E_BADARG, "negative n");
+  const FlatArrays flat = {state, state2, adam_step};
   FusedUpdate upd;
-  int rc = step_args(step, adam_step, true, &upd);
-  if (rc || n == 0) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (weights == nullptr || grads == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
-  if (step->kind == TTEMB_STEP_ADAM) {
-    if (state == nullptr || state2 == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
-    upd.w[0] = weights;
-    upd.st[0] = state;
-    upd.v[0] = state2;
-    const long long nn = n;
-    return run_adam_arrays(upd, &grads, &nn, 1, grad_scale, reinterpret_cast<const uint32_t*>(skip), st);
-  }
-  // (SGD / Adagrad: the by-value calls have no gradient scale; Adagrad has no skip word)
-  if (grad_scale != 1.f) return fail(TTEMB_E_BADARG, "flat step: grad_scale is Adam's (pass 1 for SGD / Adagrad)");
-  if (step->kind == TTEMB_STEP_SGD) return run_sgd(weights, grads, n, 0.f, st, skip, step->lr_dev);
-  if (state == nullptr) return fail(TTEMB_E_BADARG, "null buffer");
-  if (skip != nullptr) return fail(TTEMB_E_BADARG, "flat step: the Adagrad step takes no skip word");
-  return run_adagrad(weights, state, grads, n, 0.f, step->eps, st, step->lr_dev);
+  int rc = step_from_descriptor(step, n > 0 ? 1 : 0, &flat, &upd);
+  if (rc) return rc;
+  return flat_step(upd, weights, grads, n, grad_scale, skip, stream);
 }
 
 static int cache_update(const int64_t* indices, int64_t nnz, int64_t* hashtbl, int64_t* cache_freq, int64_t H, bool one_sweep,

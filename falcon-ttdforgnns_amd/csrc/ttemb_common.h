@@ -165,12 +165,28 @@ inline AdamPrep adam_prep_of(const FusedUpdate& u) {
   a.b2 = u.beta2;
   return a;
 }
-// a ttemb_adam_t into the lr, eps and Adam fields of a FusedUpdate (ttemb_api.hip); TTEMB_E_BADARG outside torch.optim.Adam's domain
-int adam_fill(const ttemb_adam_t* hp, int32_t* step, FusedUpdate* upd);
-// The Adam step of `T` arrays (upd.w / st / v [t], gradients g[t] * grad_scale, n[t] floats, all 16-byte aligned) from gradients
-// in memory: a one-lane launch that forms the pending step words, then one stepping launch (ttemb_api.hip).  skip: null, or a
-// device word that, non-zero, leaves everything as it was
-int run_adam_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
+// A FusedUpdate is the one description of an optimiser step on the host as well: v[0] != null is Adam, else st[0] != null is
+// Adagrad, else SGD; lr_dev or lr gives the rate.  The two builders below (ttemb_api.hip) are the only code that fills one from
+// an entry point's arguments, and they make every check of those arguments (TTEMB_E_BADARG).  They fill everything but `w`
+// and the poison word, which the body that runs the step sets.  `T`: the arrays the step takes (the table's cores; 1 for a flat
+// step; 0 when the call is empty or its shape will be refused, then no array is read).
+// ... from arguments by value: `kind` a TTEMB_STEP_*, `state` / `state2` the Adagrad state or Adam's moments, `hp` / `adam_step`
+// Adam's hyper-parameters (they carry its lr and eps) and step words
+int step_from_values(int32_t kind, int T, float lr, float eps, float* const* state, float* const* state2, const ttemb_adam_t* hp,
+                     int32_t* adam_step, FusedUpdate* upd);
+// ... from a descriptor, whose rate is a device word.  `flat` (a flat step): the arrays are the call's own arguments, the
+// descriptor's are not looked at
+struct FlatArrays {
+  float* state;
+  float* state2;
+  int32_t* adam_step;
+};
+int step_from_descriptor(const ttemb_step_t* step, int T, const FlatArrays* flat, FusedUpdate* upd);
+int step_arrays(const ttemb_shape_t* shape);   // the T of a lookup's step: the table's cores, 0 for a shape no call accepts
+// The step of `T` arrays (upd.w / st / v [t], gradients g[t], n[t] floats, all 16-byte aligned) from gradients in memory: for
+// Adam a one-lane launch that forms the pending step words first, then one stepping launch (ttemb_api.hip).  grad_scale
+// multiplies Adam's gradients; skip: null, or a device word that, non-zero, leaves everything as it was
+int run_step_arrays(const FusedUpdate& upd, const float* const* g, const long long* n, int T, float grad_scale, const uint32_t* skip,
                     hipStream_t st);
 
 // where that word sits in the header: behind the epoch words and the banks of range counters (16 + 8 * 512 * 8 bytes)

@@ -681,19 +681,19 @@ int ex_check_common(const ttemb_shape_t* shape, ExShape* s, const int64_t* indic
   return TTEMB_OK;
 }
 
-int ex_backward(int op, const ttemb_shape_t* shape, float* const* cores, float* const* opt_state, const int64_t* indices,
-                const int64_t* offsets, int64_t nnz, int64_t B, const float* d_output, float* const* d_cores, float lr,
-                float eps, void* workspace, int64_t workspace_bytes, void* stream, const float* lr_dev = nullptr) {
+// `step`: null for dense gradients into `d_cores`, else the SGD / Adagrad description a builder filled (its state has no null)
+int ex_backward(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets, int64_t nnz,
+                int64_t B, const float* d_output, float* const* d_cores, const FusedUpdate* step, void* workspace,
+                int64_t workspace_bytes, void* stream) {
   ExShape s;
   int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
   if (rc) return rc;
+  const int op = step == nullptr ? kExDense : step->st[0] != nullptr ? kExAdagrad : kExSgd;
   const int T = shape->T;
   for (int t = 0; t < T; ++t) {
     if (cores == nullptr || cores[t] == nullptr) return fail(TTEMB_E_BADARG, "exact mode: cores[%d] is null", t);
     if (op == kExDense && (d_cores == nullptr || d_cores[t] == nullptr))
       return fail(TTEMB_E_BADARG, "exact mode: d_cores[%d] is null", t);
-    if (op == kExAdagrad && (opt_state == nullptr || opt_state[t] == nullptr))
-      return fail(TTEMB_E_BADARG, "exact mode: opt_state[%d] is null", t);
   }
   if (nnz > 0 && B > 0 && d_output == nullptr) return fail(TTEMB_E_BADARG, "exact mode: d_output is null");
   const ExLayout L = ex_layout(s, nnz);
@@ -782,20 +782,21 @@ int ex_backward(int op, const ttemb_shape_t* shape, float* const* cores, float* 
     const int64_t rows = k == 0 ? s.mpa : s.mpb;
     const int S = k == 0 ? s.mRa * s.mqa * s.mRm : s.mRm * s.mqb * s.mRs;
     if (op == kExSgd)
-      hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], mgrad[k], mtouched[k], rows, S, lr, lr_dev);
+      hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], mgrad[k], mtouched[k], rows, S, step->lr,
+                         step->lr_dev);
     else
-      hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], opt_state[t], mgrad[k],
-                         mtouched[k], rows, S, lr, lr_dev, eps);
+      hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(rows)), dim3(kExNT), 0, st, cores[t], step->st[t], mgrad[k],
+                         mtouched[k], rows, S, step->lr, step->lr_dev, step->eps);
   }
   for (int c = 0; c < 3; ++c) {
     if (tcore[c] < 0) continue;
     float* W = cores[tcore[c]];
     if (op == kExSgd)
       hipLaunchKernelGGL(exact_sgd_kernel, dim3(ex_grid(s.p[c])), dim3(kExNT), 0, st, W, grad[c], touched[c],
-                         (int64_t)s.p[c], s.s[c], lr, lr_dev);
+                         (int64_t)s.p[c], s.s[c], step->lr, step->lr_dev);
     else
-      hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(s.p[c])), dim3(kExNT), 0, st, W, opt_state[tcore[c]], grad[c],
-                         touched[c], (int64_t)s.p[c], s.s[c], lr, lr_dev, eps);
+      hipLaunchKernelGGL(exact_adagrad_kernel, dim3(ex_grid(s.p[c])), dim3(kExNT), 0, st, W, step->st[tcore[c]], grad[c],
+                         touched[c], (int64_t)s.p[c], s.s[c], step->lr, step->lr_dev, step->eps);
   }
   return check_hip(hipGetLastError(), "exact optimiser kernel");
 }
@@ -860,8 +861,45 @@ int ttemb_backward_dense_exact(const ttemb_shape_t* shape, const float* const* c
                                void* workspace, int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream) {
   (void)plan;
   (void)plan_bytes;
-  return ex_backward(kExDense, shape, const_cast<float* const*>(cores), nullptr, indices, offsets, nnz, B, d_output, d_cores,
-                     0.0f, 0.0f, workspace, workspace_bytes, stream);
+  return ex_backward(shape, const_cast<float* const*>(cores), indices, offsets, nnz, B, d_output, d_cores, nullptr, workspace,
+                     workspace_bytes, stream);
+}
+
+// Adam: the dense exact gradient into scratch behind the exact workspace, then the elementwise step (it has no order)
+static int adam_exact(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets, int64_t nnz,
+                      int64_t B, const float* d_output, const FusedUpdate& step, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  ExShape s;
+  int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
+  if (rc) return rc;
+  if (cores == nullptr) return fail(TTEMB_E_BADARG, "exact mode: null cores / moments");
+  if (nnz == 0) return TTEMB_OK;   // a call without ids is a no-op (t stays)
+  const int64_t base = (ex_layout(s, nnz).total + 255) / 256 * 256;
+  FusedUpdate upd = step;
+  float* grads[TTEMB_MAX_CORES] = {nullptr, nullptr, nullptr, nullptr};
+  const float* g[TTEMB_MAX_CORES];
+  long long n[TTEMB_MAX_CORES];
+  int64_t off = base;
+  for (int t = 0; t < shape->T; ++t) {
+    n[t] = (long long)shape->p[t] * shape->R[t] * shape->q[t] * shape->R[t + 1];
+    g[t] = grads[t] = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + off);
+    off += (n[t] * 4 + 255) / 256 * 256;
+    upd.w[t] = cores[t];
+  }
+  if (workspace == nullptr || workspace_bytes < off)
+    return fail(TTEMB_E_WORKSPACE, "exact Adam: workspace of %lld bytes, need %lld (the exact workspace and the gradient scratch)",
+                (long long)workspace_bytes, (long long)off);
+  rc = ex_backward(shape, cores, indices, offsets, nnz, B, d_output, grads, nullptr, workspace, base, stream);
+  if (rc) return rc;
+  return run_step_arrays(upd, g, n, shape->T, 1.f, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+// body of the exact fused-step entry points: SGD and Adagrad step the rows the ids touch, Adam every row
+static int exact_step(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets, int64_t nnz,
+                      int64_t B, const float* d_output, const FusedUpdate& step, void* workspace, int64_t workspace_bytes,
+                      void* stream) {
+  if (step.v[0] != nullptr) return adam_exact(shape, cores, indices, offsets, nnz, B, d_output, step, workspace, workspace_bytes, stream);
+  return ex_backward(shape, cores, indices, offsets, nnz, B, d_output, nullptr, &step, workspace, workspace_bytes, stream);
 }
 
 int ttemb_backward_sgd_exact(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets,
@@ -869,8 +907,10 @@ int ttemb_backward_sgd_exact(const ttemb_shape_t* shape, float* const* cores, co
                              const void* plan, int64_t plan_bytes, void* stream) {
   (void)plan;
   (void)plan_bytes;
-  return ex_backward(kExSgd, shape, cores, nullptr, indices, offsets, nnz, B, d_output, nullptr, lr, 0.0f, workspace,
-                     workspace_bytes, stream);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_SGD, step_arrays(shape), lr, 0.f, nullptr, nullptr, nullptr, nullptr, &upd);
+  if (rc) return rc;
+  return exact_step(shape, cores, indices, offsets, nnz, B, d_output, upd, workspace, workspace_bytes, stream);
 }
 
 int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores, float* const* opt_state,
@@ -879,49 +919,10 @@ int ttemb_backward_adagrad_exact(const ttemb_shape_t* shape, float* const* cores
                                  const void* plan, int64_t plan_bytes, void* stream) {
   (void)plan;
   (void)plan_bytes;
-  return ex_backward(kExAdagrad, shape, cores, opt_state, indices, offsets, nnz, B, d_output, nullptr, lr, eps, workspace,
-                     workspace_bytes, stream);
-}
-
-// (lr_dev != null: the rate is that device word and hp's lr is not looked at)
-static int adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
-                      int32_t* step, const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B,
-                      const float* d_output, const ttemb_adam_t* hp_in, void* workspace, int64_t workspace_bytes,
-                      void* stream, const float* lr_dev) {
-  if (hp_in == nullptr) return fail(TTEMB_E_BADARG, "adam: null hyper-parameters / step words");
-  ttemb_adam_t hp_copy = *hp_in;
-  if (lr_dev != nullptr) hp_copy.lr = 0.f;
-  const ttemb_adam_t* hp = &hp_copy;
-  ExShape s;
-  int rc = ex_check_common(shape, &s, indices, offsets, nnz, B);
-  if (rc) return rc;
   FusedUpdate upd;
-  memset(&upd, 0, sizeof(upd));
-  if ((rc = adam_fill(hp, step, &upd))) return rc;
-  upd.lr_dev = lr_dev;
-  if (cores == nullptr || exp_avg == nullptr || exp_avg_sq == nullptr) return fail(TTEMB_E_BADARG, "exact mode: null cores / moments");
-  if (nnz == 0) return TTEMB_OK;   // a call without ids is a no-op (t stays)
-  // the dense exact gradient into scratch behind the exact workspace, then the elementwise step (it has no order)
-  const int64_t base = (ex_layout(s, nnz).total + 255) / 256 * 256;
-  float* grads[TTEMB_MAX_CORES] = {nullptr, nullptr, nullptr, nullptr};
-  const float* g[TTEMB_MAX_CORES];
-  long long n[TTEMB_MAX_CORES];
-  int64_t off = base;
-  for (int t = 0; t < shape->T; ++t) {
-    n[t] = (long long)shape->p[t] * shape->R[t] * shape->q[t] * shape->R[t + 1];
-    grads[t] = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + off);
-    g[t] = grads[t];
-    off += (n[t] * 4 + 255) / 256 * 256;
-    upd.w[t] = cores[t];
-    upd.st[t] = exp_avg[t];
-    upd.v[t] = exp_avg_sq[t];
-  }
-  if (workspace == nullptr || workspace_bytes < off)
-    return fail(TTEMB_E_WORKSPACE, "exact Adam: workspace of %lld bytes, need %lld (the exact workspace and the gradient scratch)",
-                (long long)workspace_bytes, (long long)off);
-  rc = ex_backward(kExDense, shape, cores, nullptr, indices, offsets, nnz, B, d_output, grads, 0.0f, 0.0f, workspace, base, stream);
+  int rc = step_from_values(TTEMB_STEP_ADAGRAD, step_arrays(shape), lr, eps, opt_state, nullptr, nullptr, nullptr, &upd);
   if (rc) return rc;
-  return run_adam_arrays(upd, g, n, shape->T, 1.f, nullptr, reinterpret_cast<hipStream_t>(stream));
+  return exact_step(shape, cores, indices, offsets, nnz, B, d_output, upd, workspace, workspace_bytes, stream);
 }
 
 int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, float* const* exp_avg, float* const* exp_avg_sq,
@@ -930,8 +931,10 @@ int ttemb_backward_adam_exact(const ttemb_shape_t* shape, float* const* cores, f
                               const void* plan, int64_t plan_bytes, void* stream) {
   (void)plan;
   (void)plan_bytes;
-  return adam_exact(shape, cores, exp_avg, exp_avg_sq, step, indices, offsets, nnz, B, d_output, hp, workspace, workspace_bytes, stream,
-                    nullptr);
+  FusedUpdate upd;
+  int rc = step_from_values(TTEMB_STEP_ADAM, step_arrays(shape), 0.f, 0.f, exp_avg, exp_avg_sq, hp, step, &upd);
+  if (rc) return rc;
+  return exact_step(shape, cores, indices, offsets, nnz, B, d_output, upd, workspace, workspace_bytes, stream);
 }
 
 int ttemb_backward_step_exact(const ttemb_shape_t* shape, float* const* cores, const int64_t* indices, const int64_t* offsets,
@@ -939,23 +942,10 @@ int ttemb_backward_step_exact(const ttemb_shape_t* shape, float* const* cores, c
                               int64_t workspace_bytes, const void* plan, int64_t plan_bytes, void* stream) {
   (void)plan;
   (void)plan_bytes;
-  if (step == nullptr) return fail(TTEMB_E_BADARG, "step: null descriptor");
-  if (step->lr_dev == nullptr) return fail(TTEMB_E_BADARG, "step: lr_dev is null (the by-value calls take the rate on the host)");
-  if (reinterpret_cast<uintptr_t>(step->lr_dev) & 15) return fail(TTEMB_E_BADARG, "step: lr_dev must be 16-byte aligned");
-  switch (step->kind) {
-    case TTEMB_STEP_SGD:
-      return ex_backward(kExSgd, shape, cores, nullptr, indices, offsets, nnz, B, d_output, nullptr, 0.0f, 0.0f, workspace,
-                         workspace_bytes, stream, step->lr_dev);
-    case TTEMB_STEP_ADAGRAD:
-      return ex_backward(kExAdagrad, shape, cores, step->state, indices, offsets, nnz, B, d_output, nullptr, 0.0f, step->eps,
-                         workspace, workspace_bytes, stream, step->lr_dev);
-    case TTEMB_STEP_ADAM:
-      if (step->state == nullptr || step->state2 == nullptr) return fail(TTEMB_E_BADARG, "step: state / state2 is null (Adam's moments)");
-      return adam_exact(shape, cores, step->state, step->state2, step->adam_step, indices, offsets, nnz, B, d_output, step->adam,
-                        workspace, workspace_bytes, stream, step->lr_dev);
-    default:
-      return fail(TTEMB_E_BADARG, "step: kind %d is none of TTEMB_STEP_SGD / _ADAGRAD / _ADAM", (int)step->kind);
-  }
+  FusedUpdate upd;
+  int rc = step_from_descriptor(step, step_arrays(shape), nullptr, &upd);
+  if (rc) return rc;
+  return exact_step(shape, cores, indices, offsets, nnz, B, d_output, upd, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

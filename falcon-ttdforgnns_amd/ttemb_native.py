@@ -78,23 +78,47 @@ def _lr_word(lr: torch.Tensor) -> int:
     return lr.data_ptr()
 
 
+def _fill_desc(lr: torch.Tensor, eps: float, kind: int, hp=None, state=None, state2=None, words=None) -> StepDesc:
+    """The one place a ``StepDesc`` is filled.  ``state`` / ``state2``: pointer arrays (a flat step passes none: its arrays
+    are arguments of the call); the caller keeps everything the descriptor points at alive."""
+    d = StepDesc()
+    d.kind, d.lr_dev, d.eps = kind, _lr_word(lr), float(eps)
+    if state is not None:
+        d.state = ctypes.addressof(state)
+    if state2 is not None:
+        d.state2 = ctypes.addressof(state2)
+    if hp is not None:
+        d.adam, d.adam_step = ctypes.addressof(hp), words
+    return d
+
+
+def _kind(state, hp) -> int:
+    return STEP_ADAM if hp is not None else (STEP_ADAGRAD if state is not None else STEP_SGD)
+
+
 def step_desc(lr: torch.Tensor, eps: float = 0.0, state=None, adam=None):
     """``ttemb_step_t`` of a step whose rate is the device word ``lr``: SGD (no ``state``), Adagrad (``state``: a pointer
     array or tensors) or Adam (``state`` the first moment, ``adam = (exp_avg_sq, step words, AdamParams)``; the rate in the
     ``AdamParams`` is ignored).  Returns ``(descriptor, keep)``: ``keep`` holds what the descriptor points at."""
-    d = StepDesc()
-    d.lr_dev, d.eps = _lr_word(lr), float(eps)
     st = None if state is None else _ptr_array(state)
-    st2 = None
-    if adam is not None:
-        st2 = _ptr_array(adam[0])
-        d.kind, d.state, d.state2 = STEP_ADAM, ctypes.addressof(st), ctypes.addressof(st2)
-        d.adam_step, d.adam = _ptr(adam[1]), ctypes.addressof(adam[2])
-    elif st is not None:
-        d.kind, d.state = STEP_ADAGRAD, ctypes.addressof(st)
-    else:
-        d.kind = STEP_SGD
-    return d, (st, st2, adam, lr)
+    st2, words, hp = (None, None, None) if adam is None else (_ptr_array(adam[0]), _ptr(adam[1]), adam[2])
+    return _fill_desc(lr, eps, _kind(st, hp), hp, st, st2, words), (st, st2, adam, lr)
+
+
+class Step:
+    """One optimiser step, as every stepping call below takes it.  ``lr``: a float, or a float32[1] device tensor (the rate
+    is then read on the device: the descriptor calls); ``state``: None for SGD, the Adagrad state or Adam's first moment
+    (tensors or a pointer array; one tensor for a flat step); ``adam = (exp_avg_sq, step words, AdamParams)`` makes it an
+    Adam step, whose by-value rate and eps are the ``AdamParams``' own."""
+    __slots__ = ("lr", "eps", "state", "state2", "words", "hp")
+
+    def __init__(self, lr, eps: float = 0.0, state=None, adam=None) -> None:
+        self.lr, self.eps, self.state = lr, eps, state
+        self.state2, self.words, self.hp = adam if adam is not None else (None, None, None)
+
+    @property
+    def adam(self):
+        return None if self.hp is None else (self.state2, self.words, self.hp)
 
 
 def make_adam(lr: float, eps: float, betas=(0.9, 0.999), weight_decay: float = 0.0, decoupled: bool = False) -> AdamParams:
@@ -223,6 +247,10 @@ def _load() -> ctypes.CDLL:
 
 
 LIB = _load()
+# per call family: the by-value symbols of SGD, Adagrad and Adam, then the descriptor symbol (_run_step)
+_STEP_FN = {family: tuple(getattr(LIB, "ttemb_backward_" + kind + suffix) for kind in ("sgd", "adagrad", "adam", "step"))
+            for family, suffix in (("plain", ""), ("window", "_window"), ("exact", "_exact"))}
+_STEP_FN["flat"] = (LIB.ttemb_sgd_step, LIB.ttemb_adagrad_step, LIB.ttemb_adam_step, LIB.ttemb_flat_step)
 
 
 def _check(rc: int) -> None:
@@ -259,6 +287,32 @@ def _stream(ref: torch.Tensor) -> int:
     if _raw_stream is not None:
         return _raw_stream(ref.device.index)
     return torch.cuda.current_stream(ref.device).cuda_stream
+
+
+def _run_step(family: str, step: Step, head: tuple, ids: tuple, tail: tuple, scale: tuple = ()) -> int:
+    """The one place a ``Step`` becomes a native call: picks the by-value symbol of its kind or the descriptor symbol (the
+    rate is a device tensor) of ``family`` ("plain", "window", "exact": a lookup's backward; "flat": a flat epilogue) and
+    orders the arguments.  ``head``: what precedes the optimiser's arrays (shape and cores; the weights), ``ids``: what lies
+    between them and the rate, ``tail``: the rest.  A flat step's arrays are single tensors, ``scale = (grad_scale,)`` goes
+    in front of Adam's hyper-parameters / the descriptor, and ``tail = (skip, stream)``.  Returns the status."""
+    sgd, adagrad, adam, desc = _STEP_FN[family]
+    flat = family == "flat"
+    lr, st, hp = step.lr, step.state, step.hp
+    if isinstance(lr, torch.Tensor):
+        if flat:
+            d = _fill_desc(lr, step.eps, _kind(st, hp), hp)
+            return desc(*head, _ptr(st), _ptr(step.state2), _ptr(step.words), *ids, *scale, ctypes.byref(d), *tail)
+        d, keep = step_desc(lr, step.eps, st, step.adam)
+        return desc(*head, *ids, ctypes.byref(d), *tail)
+    ptrs = _ptr if flat else _ptr_array
+    if hp is not None:
+        return adam(*head, ptrs(st), ptrs(step.state2), _ptr(step.words), *ids, *scale, ctypes.byref(hp), *tail)
+    if flat and st is None and tail[0] is not None:
+        return LIB.ttemb_sgd_step_guarded(*head, *ids, lr, *tail)
+    if flat:   # (the by-value SGD / Adagrad epilogues take no skip word)
+        assert tail[0] is None, "a by-value flat Adagrad step takes no skip word"
+        tail = tail[1:]
+    return sgd(*head, *ids, lr, *tail) if st is None else adagrad(*head, ptrs(st), *ids, lr, step.eps, *tail)
 
 
 class _on_device:
@@ -470,47 +524,37 @@ def backward_dense(shape: Shape, cores: Sequence[torch.Tensor], indices, rowidx,
                                         w.numel(), *_plan_args(plan), _stream(d_output)))
 
 
+def backward_fused(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, step: Step, ws: Workspace,
+                   plan: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None) -> None:
+    """The backward with the optimiser step ``step`` fused into it (``ttemb_backward_sgd`` / ``_adagrad`` / ``_adam``, or
+    ``ttemb_backward_step`` when the rate is a device tensor)."""
+    dev = d_output.device
+    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
+    with _on_device(dev):
+        _check(_run_step("plain", step, (ctypes.byref(shape), _ptr_array(cores)),
+                         (_ptr(indices), _ptr(rowidx), _ptr(offsets), nnz, _ptr(nnz_dev), B, _ptr(d_output)),
+                         (_ptr(w), w.numel(), *_plan_args(plan), _stream(d_output))))
+
+
 def backward_step(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, lr: torch.Tensor, ws: Workspace,
                   plan: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None, eps: float = 0.0, state=None,
                   adam=None) -> None:
     """The fused step with the rate in the device word ``lr`` (``ttemb_backward_step``): SGD, Adagrad (``state``) or Adam
     (``state`` the first moment, ``adam = (exp_avg_sq, step words, AdamParams)``)."""
-    dev = d_output.device
-    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
-    desc, keep = step_desc(lr, eps, state, adam)
-    with _on_device(dev):
-        _check(LIB.ttemb_backward_step(ctypes.byref(shape), _ptr_array(cores), _ptr(indices), _ptr(rowidx), _ptr(offsets), nnz,
-                                       _ptr(nnz_dev), B, _ptr(d_output), ctypes.byref(desc), _ptr(w), w.numel(),
-                                       *_plan_args(plan), _stream(d_output)))
-    del keep
+    _lr_word(lr)
+    backward_fused(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, Step(lr, eps, state, adam), ws, plan, offsets)
 
 
 def backward_sgd(shape: Shape, cores, indices, rowidx, nnz: int, nnz_dev, B: int, d_output, lr,
                  ws: Workspace, plan: Optional[torch.Tensor] = None, offsets: Optional[torch.Tensor] = None) -> None:
     """``lr``: a float, or a float32[1] device tensor (the rate is then read on the device: ``backward_step``)."""
-    if isinstance(lr, torch.Tensor):
-        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets)
-    dev = d_output.device
-    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
-    with _on_device(dev):
-        _check(LIB.ttemb_backward_sgd(ctypes.byref(shape), _ptr_array(cores), _ptr(indices), _ptr(rowidx),
-                                      _ptr(offsets), nnz,
-                                      _ptr(nnz_dev), B, _ptr(d_output), lr, _ptr(w), w.numel(),
-                                      *_plan_args(plan), _stream(d_output)))
+    backward_fused(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, Step(lr), ws, plan, offsets)
 
 
 def backward_adagrad(shape: Shape, cores, opt_state, indices, rowidx, nnz: int, nnz_dev, B: int, d_output,
                      lr, eps: float, ws: Workspace, plan: Optional[torch.Tensor] = None,
                      offsets: Optional[torch.Tensor] = None) -> None:
-    if isinstance(lr, torch.Tensor):   # (as in backward_sgd)
-        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets, eps, opt_state)
-    dev = d_output.device
-    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
-    with _on_device(dev):
-        _check(LIB.ttemb_backward_adagrad(ctypes.byref(shape), _ptr_array(cores), _ptr_array(opt_state),
-                                          _ptr(indices), _ptr(rowidx), _ptr(offsets), nnz, _ptr(nnz_dev), B,
-                                          _ptr(d_output),
-                                          lr, eps, _ptr(w), w.numel(), *_plan_args(plan), _stream(d_output)))
+    backward_fused(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, Step(lr, eps, opt_state), ws, plan, offsets)
 
 
 def backward_adam(shape: Shape, cores, exp_avg, exp_avg_sq, step: torch.Tensor, indices, rowidx, nnz: int, nnz_dev, B: int,
@@ -519,31 +563,22 @@ def backward_adam(shape: Shape, cores, exp_avg, exp_avg_sq, step: torch.Tensor, 
     """Fused Adam / AdamW step (``ttemb_backward_adam``): ``exp_avg`` / ``exp_avg_sq`` shaped like the cores, ``step`` the
     int32[4] device words of ``new_adam_step``.  ``lr`` (a float32[1] device tensor): the rate is read on the device and
     the one in ``hp`` ignored (``backward_step``)."""
-    if lr is not None:
-        return backward_step(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, lr, ws, plan, offsets, 0.0, exp_avg,
-                             (exp_avg_sq, step, hp))
-    dev = d_output.device
-    w = ws.get(workspace_bytes(shape, OP_BACKWARD, nnz, B), dev)
-    with _on_device(dev):
-        _check(LIB.ttemb_backward_adam(ctypes.byref(shape), _ptr_array(cores), _ptr_array(exp_avg), _ptr_array(exp_avg_sq),
-                                       _ptr(step), _ptr(indices), _ptr(rowidx), _ptr(offsets), nnz, _ptr(nnz_dev), B,
-                                       _ptr(d_output), ctypes.byref(hp), _ptr(w), w.numel(), *_plan_args(plan),
-                                       _stream(d_output)))
+    backward_fused(shape, cores, indices, rowidx, nnz, nnz_dev, B, d_output, Step(lr, 0.0, exp_avg, (exp_avg_sq, step, hp)), ws,
+                   plan, offsets)
+
+
+def _flat(weights, grads, step: Step, grad_scale: float = 1.0, skip: Optional[torch.Tensor] = None) -> None:
+    with _on_device(weights.device):
+        _check(_run_step("flat", step, (_ptr(weights),), (_ptr(grads), weights.numel()), (_ptr(skip), _stream(weights)),
+                         (grad_scale,)))
 
 
 def flat_step(weights, grads, lr: torch.Tensor, state=None, eps: float = 0.0, adam=None, grad_scale: float = 1.0,
               skip: Optional[torch.Tensor] = None) -> None:
     """A flat epilogue with the rate in the device word ``lr`` (``ttemb_flat_step``): SGD, Adagrad (``state``) or Adam
     (``state`` = exp_avg, ``adam = (exp_avg_sq, step words, AdamParams)``)."""
-    d = StepDesc()
-    d.lr_dev, d.eps = _lr_word(lr), float(eps)
-    d.kind = STEP_ADAM if adam is not None else (STEP_ADAGRAD if state is not None else STEP_SGD)
-    if adam is not None:
-        d.adam = ctypes.addressof(adam[2])
-    with _on_device(weights.device):
-        _check(LIB.ttemb_flat_step(_ptr(weights), _ptr(state), None if adam is None else _ptr(adam[0]),
-                                   None if adam is None else _ptr(adam[1]), _ptr(grads), weights.numel(), grad_scale,
-                                   ctypes.byref(d), _ptr(skip), _stream(weights)))
+    _lr_word(lr)
+    _flat(weights, grads, Step(lr, eps, state, adam), grad_scale, skip)
 
 
 def adam_step(weights, exp_avg, exp_avg_sq, step: torch.Tensor, grads, hp: AdamParams, grad_scale: float = 1.0,
@@ -551,19 +586,12 @@ def adam_step(weights, exp_avg, exp_avg_sq, step: torch.Tensor, grads, hp: AdamP
     """Flat Adam / AdamW epilogue (``ttemb_adam_step``): ``g = grads * grad_scale``; a non-zero device word ``skip[0]``
     leaves weights, moments and the step count as they are.  ``lr`` (a float32[1] device tensor): the rate is read on the
     device and the one in ``hp`` ignored."""
-    if lr is not None:
-        return flat_step(weights, grads, lr, exp_avg, adam=(exp_avg_sq, step, hp), grad_scale=grad_scale, skip=skip)
-    with _on_device(weights.device):
-        _check(LIB.ttemb_adam_step(_ptr(weights), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(step), _ptr(grads), weights.numel(),
-                                   grad_scale, ctypes.byref(hp), _ptr(skip), _stream(weights)))
+    _flat(weights, grads, Step(lr, 0.0, exp_avg, (exp_avg_sq, step, hp)), grad_scale, skip)
 
 
 def sgd_step(weights: torch.Tensor, grads: torch.Tensor, lr) -> None:
     """``lr``: a float, or a float32[1] device tensor (read on the device: ``flat_step``) -- so for every flat step."""
-    if isinstance(lr, torch.Tensor):
-        return flat_step(weights, grads, lr)
-    with _on_device(weights.device):
-        _check(LIB.ttemb_sgd_step(_ptr(weights), _ptr(grads), weights.numel(), lr, _stream(weights)))
+    _flat(weights, grads, Step(lr))
 
 
 HEADER_POISON_OFFSET = 32784   # TTEMB_HEADER_POISON_OFFSET
@@ -571,10 +599,7 @@ HEADER_POISON_OFFSET = 32784   # TTEMB_HEADER_POISON_OFFSET
 
 def sgd_step_guarded(weights: torch.Tensor, grads: torch.Tensor, lr, skip: torch.Tensor) -> None:
     """``weights -= lr * grads`` unless the device float ``skip[0]`` is non-zero (then nothing is written)."""
-    if isinstance(lr, torch.Tensor):
-        return flat_step(weights, grads, lr, skip=skip)
-    with _on_device(weights.device):
-        _check(LIB.ttemb_sgd_step_guarded(_ptr(weights), _ptr(grads), weights.numel(), lr, _ptr(skip), _stream(weights)))
+    _flat(weights, grads, Step(lr), skip=skip)
 
 
 def poison_word(ws: "Workspace") -> Optional[torch.Tensor]:
@@ -586,11 +611,7 @@ def poison_word(ws: "Workspace") -> Optional[torch.Tensor]:
 
 
 def adagrad_step(weights, state, grads, lr, eps: float) -> None:
-    if isinstance(lr, torch.Tensor):
-        return flat_step(weights, grads, lr, state, eps)
-    with _on_device(weights.device):
-        _check(LIB.ttemb_adagrad_step(_ptr(weights), _ptr(state), _ptr(grads), weights.numel(), lr, eps,
-                                      _stream(weights)))
+    _flat(weights, grads, Step(lr, eps, state))
 
 
 E_UNSUPPORTED = -3
@@ -632,20 +653,12 @@ def backward_window(shape: Shape, cores: Sequence[torch.Tensor], indices: torch.
     w = ws.get(window_workspace_bytes(shape, OP_BACKWARD, nnz, bags, B), dev)
     head = (ctypes.byref(shape), _ptr_array(cores))
     ids = (_ptr(indices), _ptr(offsets), nnz, bags, bag0, B, _ptr(d_output))
+    tail = (_ptr(w), w.numel(), _stream(d_output))
     with _on_device(dev):
         if d_cores is not None:
-            _check(LIB.ttemb_backward_dense_window(*head, *ids, _ptr_array(d_cores), _ptr(w), w.numel(), _stream(d_output)))
-        elif isinstance(lr, torch.Tensor):
-            desc, keep = step_desc(lr, eps, opt_state, adam)
-            _check(LIB.ttemb_backward_step_window(*head, *ids, ctypes.byref(desc), _ptr(w), w.numel(), _stream(d_output)))
-            del keep
-        elif adam is not None:
-            _check(LIB.ttemb_backward_adam_window(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
-                                                  ctypes.byref(adam[2]), _ptr(w), w.numel(), _stream(d_output)))
-        elif opt_state is None:
-            _check(LIB.ttemb_backward_sgd_window(*head, *ids, lr, _ptr(w), w.numel(), _stream(d_output)))
+            _check(LIB.ttemb_backward_dense_window(*head, *ids, _ptr_array(d_cores), *tail))
         else:
-            _check(LIB.ttemb_backward_adagrad_window(*head, _ptr_array(opt_state), *ids, lr, eps, _ptr(w), w.numel(), _stream(d_output)))
+            _check(_run_step("window", Step(lr, eps, opt_state, adam), head, ids, tail))
 
 
 def exact_workspace_bytes(shape: Shape, nnz: int, B: int) -> int:
@@ -706,17 +719,8 @@ def backward_exact(shape: Shape, cores, indices: torch.Tensor, offsets: torch.Te
     with _on_device(dev):
         if d_cores is not None:
             _check(LIB.ttemb_backward_dense_exact(*head, *ids, _ptr_array(d_cores), *tail))
-        elif isinstance(lr, torch.Tensor):
-            desc, keep = step_desc(lr, eps, opt_state, adam)
-            _check(LIB.ttemb_backward_step_exact(*head, *ids, ctypes.byref(desc), *tail))
-            del keep
-        elif adam is not None:
-            _check(LIB.ttemb_backward_adam_exact(*head, _ptr_array(opt_state), _ptr_array(adam[0]), _ptr(adam[1]), *ids,
-                                                 ctypes.byref(adam[2]), *tail))
-        elif opt_state is None:
-            _check(LIB.ttemb_backward_sgd_exact(*head, *ids, lr, *tail))
         else:
-            _check(LIB.ttemb_backward_adagrad_exact(*head, _ptr_array(opt_state), *ids, lr, eps, *tail))
+            _check(_run_step("exact", Step(lr, eps, opt_state, adam), head, ids, tail))
 
 
 def bag_workspace_bytes(nnz: int, B: int, D: int) -> int:
@@ -1071,6 +1075,7 @@ class LeanCalls:
         self.state_key, self.state_arr = None, None
         self.state2_key, self.state2_arr = None, None   # (Adam: the second moment)
         self.grad_key, self.grad_arr = None, None
+        self.step = Step(0.0)   # (reused by every backward: no object per call)
 
     def _entry(self, nnz: int, B: int):
         if self.epoch != path_epoch:
@@ -1159,35 +1164,17 @@ class LeanCalls:
         dev = d_output.device
         w = self.ws.get(bwd_ws, dev)
         pp, pn = (plan.data_ptr(), plan_n) if plan is not None else (None, 0)
-        ids = indices.data_ptr() if nnz else None
-        cnt = None if nnz_dev is None else nnz_dev.data_ptr()
+        if state is not None:
+            self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
+            state = self.state_arr
+        if adam is not None:
+            self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
+            adam = (self.state2_arr, adam[1], adam[2])
+        self.step.__init__(lr, eps, state, adam)
         with _on_device(dev):
-            if isinstance(lr, torch.Tensor):
-                d = StepDesc()
-                d.lr_dev, d.eps = _lr_word(lr), eps
-                if state is not None:
-                    self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
-                    d.kind, d.state = STEP_ADAGRAD, ctypes.addressof(self.state_arr)
-                if adam is not None:
-                    self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
-                    d.kind, d.state2 = STEP_ADAM, ctypes.addressof(self.state2_arr)
-                    d.adam_step, d.adam = adam[1].data_ptr(), ctypes.addressof(adam[2])
-                rc = LIB.ttemb_backward_step(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, cnt, B,
-                                             d_output.data_ptr() if B else None, ctypes.byref(d), w.data_ptr(), w.numel(), pp, pn,
-                                             _stream(d_output))
-            elif adam is not None:
-                self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
-                self.state2_key, self.state2_arr = self._ptrs(adam[0], self.state2_key, self.state2_arr)
-                rc = LIB.ttemb_backward_adam(self.shape_ref, self.core_arr, self.state_arr, self.state2_arr, adam[1].data_ptr(), ids,
-                                             None, offsets.data_ptr(), nnz, cnt, B, d_output.data_ptr() if B else None,
-                                             ctypes.byref(adam[2]), w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
-            elif state is None:
-                rc = LIB.ttemb_backward_sgd(self.shape_ref, self.core_arr, ids, None, offsets.data_ptr(), nnz, cnt, B,
-                                            d_output.data_ptr() if B else None, lr, w.data_ptr(), w.numel(), pp, pn, _stream(d_output))
-            else:
-                self.state_key, self.state_arr = self._ptrs(state, self.state_key, self.state_arr)
-                rc = LIB.ttemb_backward_adagrad(self.shape_ref, self.core_arr, self.state_arr, ids, None, offsets.data_ptr(), nnz, cnt,
-                                                B, d_output.data_ptr() if B else None, lr, eps, w.data_ptr(), w.numel(), pp, pn,
-                                                _stream(d_output))
+            rc = _run_step("plain", self.step, (self.shape_ref, self.core_arr),
+                           (indices.data_ptr() if nnz else None, None, offsets.data_ptr(), nnz,
+                            None if nnz_dev is None else nnz_dev.data_ptr(), B, d_output.data_ptr() if B else None),
+                           (w.data_ptr(), w.numel(), pp, pn, _stream(d_output)))
         if rc:
             _check(rc)

@@ -156,6 +156,69 @@ def test_call_in_pieces_within_the_fp32_bound(nat):
     _check_all("pieces", "grouped", p, q, R, R, cores, ids, offs, dy, st0, *res, pieces=pieces)
 
 
+# Adagrad behind the routes that write gradients first and step them afterwards, one launch for every core: padded ranks, the
+# merged views of a 4-core and of a 2-core table on the grouped kernels, a call in pieces, and the tiny 2- and 4-core tables
+# of test_gpu_device_lr.py on whatever kernels the library picks for them (none of which steps by itself).  Shapes and id
+# counts of test_gpu_device_lr.py (test_padded_rank, test_two_and_four_core_tables, test_a_call_in_pieces); the grouped
+# merged views need the larger tables of ABI_CASES.  One id per bag, as there.
+# (key, p, q, inner ranks, ids, path, piece limit, family & 7 or None, route flag that must be set, kernel ranks)
+STEP_CASES = [
+    ("padded_rank", [8, 10, 10], [4, 5, 5], [12, 12], 4096, "fast3", 0, 3, 32, [16, 16]),
+    ("merged_4core", [12, 9, 14, 11], [5, 5, 2, 2], [16, 16, 16], 4096, "fast3", 0, 3, 16, None),
+    ("lifted_2core", [7, 33], [16, 8], [16], 4096, "fast3", 0, 3, 16, None),
+    ("pieces", [8, 10, 10], [4, 5, 5], [16, 16], 4096, "fast3", 1400, 3, 0, None),
+    ("tiny_2core", [6, 7], [4, 3], [5], 300, "auto", 0, None, 0, None),
+    ("tiny_4core", [3, 2, 4, 3], [2, 2, 3, 2], [3, 4, 2], 300, "auto", 0, None, 0, None),
+]
+
+
+@pytest.mark.parametrize("case", STEP_CASES, ids=[c[0] for c in STEP_CASES])
+def test_adagrad_step_behind_a_gradient_writing_route(nat, case):
+    """The rate by value and from a device word: cores and state of both against the float64 oracle, per element, with the
+    bound the fused Adagrad case of test_route_within_the_fp32_bound uses.  The two results are not compared with each
+    other: these routes sum with float atomics, so two runs of ONE call differ as well, by up to twice that bound on these
+    ill-conditioned inputs (test_gpu_device_lr.py compares the twins on the same routes, on inputs its tolerances fit)."""
+    key, p, q, r, n, path, limit, want_fam, flag, rk = case
+    R, Rk = [1] + r + [1], [1] + (rk or r) + [1]
+    rng = np.random.default_rng(len(key) + n)
+    cores = fb.scaled_cores(rng, p, q, R)
+    ids = rng.integers(0, int(np.prod(p)), size=n).astype(np.int64)
+    offs = np.arange(n + 1, dtype=np.int64)
+    dy = fb.scaled_dy(rng, n, int(np.prod(q)))
+    st0 = [(rng.random(c.shape) * 1e-6).astype(np.float32) for c in cores]
+    shape, ws = nat.make_shape(p, q, R), nat.Workspace()
+    try:
+        nat.set_path(nat.PATH_FAST3 if path == "fast3" else nat.PATH_AUTO)
+        nat.set_piece_limits(limit, limit)
+        fam = nat.kernel_family(shape, n, n, True)
+        assert fam & 7 == (want_fam if want_fam is not None else fam & 7) and fam & flag == flag, (key, fam)
+        # ... and not the one route whose last kernel applies the step itself (grouped, no view, one piece)
+        assert fam & 7 != nat.FAMILY_GROUPED or fam & (nat.FAMILY_MERGED | nat.FAMILY_PADDED) or limit, (key, fam)
+        if limit:
+            assert nat.plan_bytes(shape, n) == 0   # a call in pieces keeps no plan
+        I, O, dY = _dev(ids), _dev(offs), _dev(dy)
+        got = []
+        for lr in (LR, torch.full((1,), LR, dtype=torch.float32, device="cuda")):
+            ca, st = [_dev(x) for x in cores], [_dev(x) for x in st0]
+            nat.backward_adagrad(shape, ca, st, I, None, n, None, n, dY, lr, EPS, ws, None, O)
+            torch.cuda.synchronize()
+            got.append(([x.cpu().numpy() for x in ca], [x.cpu().numpy() for x in st]))
+        nat.status()
+    finally:
+        nat.set_path(nat.PATH_AUTO)
+        nat.set_piece_limits(0, 0)
+    route = _route(fam, nat)
+    pieces = 2 * -(-n // limit) + 1 if limit else 0
+    ref = orc.tt_dense_backward64(ids, offs, dy, cores, p, q, R)
+    for t, (v, m, cnt) in enumerate(ref):
+        delta = fb.gamma(fb.grad_depth(route, q, Rk, t, cnt, merged=len(p) != 3, pieces=pieces)) * m
+        for (ada, ada_st), src in zip(got, ("by value", "device word")):
+            what = f"{key} Adagrad, rate {src}, core {t}"
+            _note("step_" + key, fb.assert_adagrad_grade(ada[t], ada_st[t], cores[t], st0[t], v, delta, LR, EPS, what))
+            fb.assert_untouched(ada[t], cores[t], cnt, what)
+            fb.assert_untouched(ada_st[t], st0[t], cnt, what + " state")
+
+
 def test_three_table_windows_within_the_fp32_bound(nat):
     p, q, R = [20, 25, 300], [4, 5, 5], [1, 16, 16, 1]
     nat.set_path(nat.PATH_AUTO)

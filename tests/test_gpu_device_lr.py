@@ -313,7 +313,7 @@ def test_products_table_where_the_chain_forms_its_prefix_products(ops, nat, opti
                                           lambda ref: dict(rtol=1e-4, atol=1e-6 if sgd else 2e-5)))
 
 
-@pytest.mark.parametrize("optimizer", ["SGD", "ADAM"])
+@pytest.mark.parametrize("optimizer", ["SGD", "ADAM", "EXACT_ADAGRAD"])
 def test_padded_rank(ops, nat, optimizer):
     """Rank 12 rides on the rank-16 grouped kernels through padded cores: gradients into scratch, then the step kernel.
     Tolerances of test_gpu_module.py::test_captured_lookup_trains_like_the_eager_module (same table, same sizes)."""
@@ -324,7 +324,7 @@ def test_padded_rank(ops, nat, optimizer):
 
 
 @pytest.mark.parametrize("shape", ["T2", "T4"])
-@pytest.mark.parametrize("optimizer", ["SGD", "ADAM"])
+@pytest.mark.parametrize("optimizer", ["SGD", "ADAM", "EXACT_ADAGRAD"])
 def test_two_and_four_core_tables(ops, nat, optimizer, shape):
     """The shapes of the golden cases tt_tiny_T2 / tt_tiny_T4 (a merged 3-core view, or the scalar kernels: gradients into
     scratch, then the step kernel).  Tolerances as test_padded_rank."""
@@ -332,7 +332,7 @@ def test_two_and_four_core_tables(ops, nat, optimizer, shape):
     _two_steps(ops, nat, optimizer, (300, 41), p=p, q=q, r=r, n_emb=int(np.prod(p)))
 
 
-@pytest.mark.parametrize("optimizer", ["SGD", "ADAM"])
+@pytest.mark.parametrize("optimizer", ["SGD", "ADAM", "EXACT_ADAGRAD"])
 def test_a_call_in_pieces(ops, nat, optimizer):
     """Piece limits of 1 400 ids: 4096 ids run as three pieces, whose summed gradient is stepped once.  Tolerances as
     test_padded_rank."""
