@@ -21,6 +21,7 @@ CPU tensors raises ``RuntimeError``.
 """
 from __future__ import annotations
 
+import gc
 import logging
 import math
 import warnings
@@ -565,6 +566,23 @@ class _PadWeights(torch.autograd.Function):
         return out, None, None, None, None
 
 
+class _quiet_collector:
+    """Around the stream captures of ``capture()`` / ``capture_bags()``: one full collection first, then none until the
+    captures are done.  Python's cyclic collector runs whenever enough objects have been allocated, also in the middle of a
+    capture, and it runs the destructors of whatever dead cycle it finds -- a dead cycle that holds HIP graphs or device
+    memory then frees them while this thread captures, which the runtime refuses in global capture mode: the process aborts.
+    (``torch.cuda.graph`` used to collect before every capture and no longer does.)"""
+
+    def __enter__(self) -> None:
+        gc.collect()
+        self.was_enabled = gc.isenabled()
+        gc.disable()
+
+    def __exit__(self, *exc) -> None:
+        if self.was_enabled:
+            gc.enable()
+
+
 class _ReplayLookup(torch.autograd.Function):
     """Autograd node of a captured lookup: forward and backward are one HIP-graph replay each.  ``n_live`` / ``B_live``: None
     for a fixed capture; the ids and bags of a ``capture(..., variable=True)`` call, already staged -- the forward then hands
@@ -576,7 +594,9 @@ class _ReplayLookup(torch.autograd.Function):
                 B_live: Optional[int] = None) -> torch.Tensor:
         ctx.cap, ctx.n_live, ctx.B_live = cap, n_live, B_live
         cap.fwd_graph.replay()
-        return cap.output if B_live is None else cap.output[:B_live]
+        # (always a VIEW of the static buffer: handing out the buffer itself would give it this node as its grad_fn, a
+        #  reference cycle cap -> output -> node -> cap that only the cyclic collector frees -- see _quiet_collector)
+        return cap.output[:] if B_live is None else cap.output[:B_live]
 
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
@@ -680,10 +700,11 @@ class CapturedLookup:
         torch.cuda.synchronize(dev)
         _nat.init()   # the pinned fault word exists before anything is captured (a capture must not allocate it)
         self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.fwd_graph):
-            fwd()
-        with torch.cuda.graph(self.bwd_graph):   # (a zero gradient: the captured update leaves the cores as they are)
-            bwd()
+        with _quiet_collector():
+            with torch.cuda.graph(self.fwd_graph):
+                fwd()
+            with torch.cuda.graph(self.bwd_graph):   # (a zero gradient: the captured update leaves the cores as they are)
+                bwd()
         if saved is not None:
             with torch.no_grad():
                 for t, t0 in zip((*cores, *state, *adam[0], module.adam_step), saved):
@@ -760,7 +781,7 @@ class _ReplayBags(torch.autograd.Function):
         ctx.cap, ctx.n_live, ctx.B_live = cap, n_live, B_live
         ctx.w_shape = None if weights is None else weights.shape
         cap.fwd_graph.replay()
-        return cap.output[:B_live] if cap.variable else cap.output
+        return cap.output[:B_live] if cap.variable else cap.output[:]   # (a view in both cases: _ReplayLookup.forward)
 
     @staticmethod
     def backward(ctx, d_output: torch.Tensor):
@@ -789,7 +810,18 @@ class CapturedBags(CapturedLookup):
     and ``ttemb_bag_mean`` in place; the unweighted unpadded sum is the plain lookup; everything else looks the ids up as
     bags of one into a static ``rows[nnz, D]`` and pools them (``ttemb_bag_reduce_n`` with the call's weights or those of
     ``ttemb_pad_weights_n``, ``ttemb_bag_max_n``), the backward pooling into a static ``d_rows[nnz, D]`` the lookup's
-    backward takes.  A padded call always takes these masked rows.
+    backward takes.  A padded call takes these masked rows (every pad position is looked up, and pooled with weight 0) unless
+    the capture asks for ``pad_route="partition"``.
+
+    ``pad_route="partition"`` (a module with ``padding_idx``; not in exact mode): the FIRST node of the forward graph
+    (``ttemb_compact_bags``) drops the pad ids of the staged call on the device -- kept ids, their weights and the compacted
+    offsets into static buffers of their own, the kept count into a device word -- and everything behind it, in both graphs,
+    runs on those with that word as its id count: routed as if the module had no padding (``cap.route``), so the unweighted
+    sum and mean own no ``rows`` / ``d_rows`` at all, a mean divides by the kept lengths and a bag of pads only is an empty
+    bag.  The weight gradient goes back to the call's positions by a gather (``ttemb_expand_kept``): exactly 0 at a pad.  A
+    call whose ids are ALL pads replays the backward with a kept count of 0: no core row is touched, so SGD and Adagrad
+    leave cores and state as they are, while Adam -- whose step is dense -- counts a step (``t`` advances, ``m`` and ``v``
+    decay), as an eager call of pads only does too.  ``cap.pad_route`` tells which ("partition", "masked", None: no padding).
 
     ``variable=True``: ``nnz`` and ``B`` are capacities; one launch (``ttemb_stage_bags``) puts ids, offsets (or, with
     ``fanout``, the offsets it generates) and weights into the static buffers and leaves the id count in the device word every
@@ -798,11 +830,16 @@ class CapturedBags(CapturedLookup):
     autograd (one copy of ``n`` floats) when the call's weights require it.  DESIGN.md §4.13."""
 
     _MODES = ("sum", "mean", "max")
+    _PAD_ROUTES = (None, "masked", "partition")
 
     @staticmethod
     def check_arguments(module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str], weighted: bool,
-                        fanout: Optional[int]) -> str:
+                        fanout: Optional[int], pad_route: Optional[str] = None) -> str:
         """The argument errors of ``capture_bags``, raised before a device is touched; returns the effective mode."""
+        if pad_route not in CapturedBags._PAD_ROUTES:
+            raise ValueError(f"pad_route must be None, 'masked' or 'partition', got {pad_route!r}")
+        if pad_route == "partition" and module.padding_idx is None:
+            raise ValueError("pad_route='partition' drops the ids equal to padding_idx: this module has none")
         if mode is None:
             mode = module.mode
         elif mode not in CapturedBags._MODES:
@@ -821,8 +858,8 @@ class CapturedBags(CapturedLookup):
         return mode
 
     def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str] = None, weighted: bool = False,
-                 fanout: Optional[int] = None, variable: bool = False) -> None:
-        mode = self.check_arguments(module, nnz, B, mode, weighted, fanout)
+                 fanout: Optional[int] = None, variable: bool = False, pad_route: Optional[str] = None) -> None:
+        mode = self.check_arguments(module, nnz, B, mode, weighted, fanout, pad_route)
         if module.use_cache and not module.warmup:
             raise RuntimeError("capture_bags() with a live row cache is not supported")
         self.module, self.nnz, self.B = module, int(nnz), int(B)
@@ -836,11 +873,20 @@ class CapturedBags(CapturedLookup):
                 f"capture_bags(nnz={self.nnz}, B={self.B}, variable=True) is not served in exact mode (OptimType.EXACT_SGD / "
                 "deterministic): the exact kernels take no device id count, so a call shorter than the capacity would not "
                 "reproduce the eager call bit for bit.  Use variable=False, or a module outside exact mode.")
+        part = pad_route == "partition"
+        if part and self.exact:
+            raise RuntimeError(
+                f"capture_bags(nnz={self.nnz}, B={self.B}, pad_route='partition') is not served in exact mode "
+                "(OptimType.EXACT_SGD / deterministic): the exact kernels take no device id count, and the count of the kept "
+                "ids exists on the device only.  Use pad_route='masked', or a module outside exact mode.")
+        # how the pads are left out: "partition" (compacted away in front of everything else), "masked" (looked up, weight 0)
+        self.pad_route = "partition" if part else ("masked" if self.pad is not None else None)
+        mask_pad = None if part else self.pad   # the pad id the pooling kernels have to mask; none once the ids are compacted
         nnz, B, D = self.nnz, self.B, module.embedding_dim
         dev = module.tt_cores[0].device
         f32 = dict(dtype=torch.float32, device=dev)
         # which route: "plain" (the lookup pools), "mean" (the lookup, then the division), "rows" (bags of one, then the pooling)
-        self.route = "rows" if (mode == "max" or self.weighted or self.pad is not None) else ("mean" if mode == "mean" else "plain")
+        self.route = "rows" if (mode == "max" or self.weighted or mask_pad is not None) else ("mean" if mode == "mean" else "plain")
         self.indices = torch.zeros(nnz, dtype=torch.int64, device=dev)
         # until the first call: one bag that holds every id, the others empty (variable: no id at all)
         self.offsets = torch.full((B + 1,), 0 if self.variable else nnz, dtype=torch.int64, device=dev)
@@ -849,6 +895,18 @@ class CapturedBags(CapturedLookup):
             self.offsets.copy_(torch.arange(B + 1, dtype=torch.int64, device=dev) * self.fanout)
         self.nnz_dev = torch.zeros(1, dtype=torch.int32, device=dev) if self.variable else None
         self.weights = torch.zeros(nnz, **f32) if self.weighted else None
+        # what the graphs' lookups and poolings run on: the staged call, or (partition) what ttemb_compact_bags makes of it
+        # as the first node of the forward graph -- kept ids, their bags and weights, the kept count as the count word
+        self.ids_k = self.offsets_k = self.weights_k = self.map = self.kept_dev = self._pad_ws = None
+        ids, offs, wts, cnt = self.indices, self.offsets, self.weights, self.nnz_dev
+        if part:
+            self.ids_k = torch.zeros(nnz, dtype=torch.int64, device=dev)
+            self.offsets_k = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+            self.kept_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._pad_ws = torch.zeros(_nat.compact_bags_workspace_bytes(nnz), dtype=torch.uint8, device=dev)   # tile counts
+            if self.weighted:   # (the map is the way back of the weight gradient)
+                self.weights_k, self.map = torch.zeros(nnz, **f32), torch.full((nnz,), -1, dtype=torch.int32, device=dev)
+            ids, offs, wts, cnt = self.ids_k, self.offsets_k, self.weights_k, self.kept_dev
         self.output = torch.zeros((B, D), **f32)
         self.d_output = torch.zeros_like(self.output)
         self.d_sums = torch.zeros_like(self.output) if self.route == "mean" else None
@@ -861,10 +919,11 @@ class CapturedBags(CapturedLookup):
                 self.argmax = torch.full((B, D), -1, dtype=torch.int32, device=dev)
             else:
                 # what the pooling multiplies with: the call's weights, or those ttemb_pad_weights_n makes of them
-                self.pool_weights = torch.zeros(nnz, **f32) if self.pad is not None else self.weights
+                self.pool_weights = torch.zeros(nnz, **f32) if mask_pad is not None else wts
             if self.weighted:
                 self.d_weights = torch.zeros(nnz, **f32)
-                # (padded: the gradient of the masked weights goes through the mask once more, as the eager _PadWeights does)
+                # (masked: the gradient of the masked weights goes through the mask once more, as the eager _PadWeights does;
+                #  partition: the gradient of the kept weights goes back to the call's positions, ttemb_expand_kept)
                 self.d_weights_out = torch.zeros(nnz, **f32) if self.pad is not None else self.d_weights
         self._lean = _nat.LeanCalls(module._shape, _nat.Workspace())   # private workspace: pinned for the graphs' lifetime
         self.plan = None
@@ -873,53 +932,56 @@ class CapturedBags(CapturedLookup):
         lr, eps = module._lr_arg(), float(module.eps)   # (capturable: the device word, brought up to date; held by address)
         adam = module._adam_lean()
         self._adam_key = module._adam_key()
-        ws, cnt, shape = self._lean.ws, self.nnz_dev, module._shape
+        ws, shape = self._lean.ws, module._shape
         rows_route = self.route == "rows"
         # the lookup inside the graphs: (ids, bags, destination) forward, (ids, bags, gradient) backward
-        look_offs, look_B = (self.ones, nnz) if rows_route else (self.offsets, B)
+        look_offs, look_B = (self.ones, nnz) if rows_route else (offs, B)
         look_out = self.rows if rows_route else self.output
         look_grad = self.d_rows if rows_route else (self.d_sums if self.route == "mean" else self.d_output)
 
         def lookup_forward():
             if self.exact:
-                _nat.forward_exact(shape, _nat.core_ptrs(cores), self.indices, look_offs, look_B, look_out, ws)
+                _nat.forward_exact(shape, _nat.core_ptrs(cores), ids, look_offs, look_B, look_out, ws)
             else:   # (variable: the route is chosen from the capacities, on the host; the kernels read the live count)
-                self.plan = self._lean.forward(cores, self.indices, look_offs, nnz, look_B, look_out, nnz_dev=cnt)
+                self.plan = self._lean.forward(cores, ids, look_offs, nnz, look_B, look_out, nnz_dev=cnt)
 
         def lookup_backward():
             if self.exact:
-                _nat.backward_exact(shape, _nat.core_ptrs(cores), self.indices, look_offs, look_B, look_grad, ws,
+                _nat.backward_exact(shape, _nat.core_ptrs(cores), ids, look_offs, look_B, look_grad, ws,
                                     opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps,
                                     adam=None if adam is None else (_nat.core_ptrs(adam[0]), adam[1], adam[2]))
             else:
-                self._lean.backward(cores, state, self.indices, look_offs, nnz, look_B, look_grad, lr, eps, self.plan, adam,
+                self._lean.backward(cores, state, ids, look_offs, nnz, look_B, look_grad, lr, eps, self.plan, adam,
                                     nnz_dev=cnt)
 
         def fwd():
+            if part:   # the first node: pads out, kept count into the word every kernel behind it stops at
+                _nat.compact_bags(self.indices, self.offsets, self.weights, self.pad, self.ids_k, self.offsets_k, self.weights_k,
+                                  self.map, self.kept_dev, self._pad_ws, nnz_dev=self.nnz_dev)
             lookup_forward()
             if self.route == "mean":
-                _nat.bag_mean(self.output, self.output, self.offsets)
+                _nat.bag_mean(self.output, self.output, offs)
             elif rows_route and mode == "max":
-                _nat.bag_max(self.rows, self.offsets, self.output, self.argmax, ws, None if self.pad is None else self.indices,
-                             self.pad or 0, nnz_dev=cnt, counted=True)
+                _nat.bag_max(self.rows, offs, self.output, self.argmax, ws, None if mask_pad is None else ids,
+                             mask_pad or 0, nnz_dev=cnt, counted=True)
             elif rows_route:
-                if self.pad is not None:
-                    _nat.pad_weights(self.indices, self.offsets, self.weights, self.pad, mode == "mean", self.pool_weights,
-                                     nnz_dev=cnt, counted=True)
-                _nat.bag_reduce(self.rows, self.pool_weights, self.offsets, self.output, ws, nnz_dev=cnt, counted=True)
+                if mask_pad is not None:
+                    _nat.pad_weights(ids, offs, wts, mask_pad, mode == "mean", self.pool_weights, nnz_dev=cnt, counted=True)
+                _nat.bag_reduce(self.rows, self.pool_weights, offs, self.output, ws, nnz_dev=cnt, counted=True)
 
-        def bwd():
+        def bwd():   # (partition: on the compacted buffers the forward replay left)
             if self.route == "mean":
-                _nat.bag_mean(self.d_output, self.d_sums, self.offsets)
+                _nat.bag_mean(self.d_output, self.d_sums, offs)
             elif rows_route and mode == "max":
-                _nat.bag_max_backward(self.d_output, self.argmax, self.offsets, self.d_rows, nnz_dev=cnt, counted=True)
+                _nat.bag_max_backward(self.d_output, self.argmax, offs, self.d_rows, nnz_dev=cnt, counted=True)
             elif rows_route:
-                _nat.bag_reduce_backward(self.d_output, self.pool_weights, self.offsets, self.d_rows, ws,
+                _nat.bag_reduce_backward(self.d_output, self.pool_weights, offs, self.d_rows, ws,
                                          rows=self.rows if self.weighted else None, d_weights=self.d_weights, nnz_dev=cnt,
                                          counted=True)
-                if self.weighted and self.pad is not None:
-                    _nat.pad_weights(self.indices, self.offsets, self.d_weights, self.pad, False, self.d_weights_out,
-                                     nnz_dev=cnt, counted=True)
+                if self.weighted and mask_pad is not None:
+                    _nat.pad_weights(ids, offs, self.d_weights, mask_pad, False, self.d_weights_out, nnz_dev=cnt, counted=True)
+                elif self.weighted and part:   # a pad's weight gradient is exactly 0
+                    _nat.expand_kept(self.d_weights, self.map, self.d_weights_out, nnz_dev=self.nnz_dev)
             lookup_backward()
 
         # The warm-up runs one backward on a zero gradient outside the capture (workspace growth, LDS-size attributes and size
@@ -936,10 +998,11 @@ class CapturedBags(CapturedLookup):
         torch.cuda.synchronize(dev)
         _nat.init()   # the pinned fault word exists before anything is captured (a capture must not allocate it)
         self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.fwd_graph):
-            fwd()
-        with torch.cuda.graph(self.bwd_graph):
-            bwd()
+        with _quiet_collector():
+            with torch.cuda.graph(self.fwd_graph):
+                fwd()
+            with torch.cuda.graph(self.bwd_graph):
+                bwd()
         with torch.no_grad():
             for t, t0 in zip(held, saved):
                 t.copy_(t0)
@@ -1281,12 +1344,15 @@ class TableBatchedTTEmbeddingBag(nn.Module):
         return CapturedLookup(self, nnz, B, offsets, variable)
 
     def capture_bags(self, nnz: int, B: int, *, mode: Optional[str] = None, weighted: bool = False,
-                     fanout: Optional[int] = None, variable: bool = False) -> CapturedBags:
+                     fanout: Optional[int] = None, variable: bool = False,
+                     pad_route: Optional[str] = None) -> CapturedBags:
         """Pooled lookup whose forward and backward replay captured HIP graphs (see ``CapturedBags``): ``mode`` ("sum",
         "mean", "max"; None = the module's), ``weighted`` (every call brings ``per_sample_weights``), the module's
         ``padding_idx``, ``fanout=N`` (2-D ``indices[rows, N]``, ``nnz == B * N``) -- of exactly ``nnz`` ids in ``B`` bags, or,
-        with ``variable=True``, of any size up to those capacities."""
-        return CapturedBags(self, nnz, B, mode, weighted, fanout, variable)
+        with ``variable=True``, of any size up to those capacities.  ``pad_route="partition"`` (a module with
+        ``padding_idx``, outside exact mode): the pad ids are dropped on the device as the first node of the forward graph and
+        never reach the TT kernels; None / ``"masked"``: they are looked up and pooled with weight 0."""
+        return CapturedBags(self, nnz, B, mode, weighted, fanout, variable, pad_route)
 
     # ---- lookup -------------------------------------------------------------------
     def _cores(self) -> tuple:

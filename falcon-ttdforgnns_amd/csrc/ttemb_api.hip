@@ -1718,6 +1718,37 @@ int ttemb_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t n
                              reinterpret_cast<hipStream_t>(stream));
 }
 
+int64_t ttemb_compact_bags_workspace_bytes(int64_t nnz) {
+  if (nnz < 0) return fail(TTEMB_E_BADARG, "ttemb_compact_bags_workspace_bytes: negative size");
+  return kFast3HeaderBytes + compact_bags_workspace_bytes(nnz);
+}
+
+int ttemb_compact_bags(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, const int32_t* nnz_dev,
+                       int64_t B, int64_t pad, int64_t* indices_out, int64_t* offsets_out, float* weights_out, int32_t* map_out,
+                       int32_t* kept_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  ApiRange api_range("ttemb_compact_bags");
+  if (nnz < 0 || B < 0) return fail(TTEMB_E_BADARG, "ttemb_compact_bags: negative size");
+  if (nnz > 0x7fffffffll) return fail(TTEMB_E_BADARG, "ttemb_compact_bags: nnz exceeds int32 range");
+  if (!offsets || !offsets_out || !kept_dev || !workspace || (nnz > 0 && (!indices || !indices_out)))
+    return fail(TTEMB_E_BADARG, "ttemb_compact_bags: null buffer");
+  if ((weights == nullptr) != (weights_out == nullptr))
+    return fail(TTEMB_E_BADARG, "ttemb_compact_bags: weights and weights_out are both given or both NULL");
+  if (nnz > 0 && indices_out == indices) return fail(TTEMB_E_BADARG, "ttemb_compact_bags: the partition cannot run in place");
+  if (workspace_bytes < kFast3HeaderBytes) return fail(TTEMB_E_WORKSPACE, "ttemb_compact_bags: workspace smaller than its header");
+  return launch_compact_bags(indices, offsets, weights, nnz, nnz_dev, B, pad, indices_out, offsets_out, weights_out, map_out,
+                             kept_dev, reinterpret_cast<char*>(workspace) + kFast3HeaderBytes,
+                             workspace_bytes - kFast3HeaderBytes, reinterpret_cast<hipStream_t>(stream));
+}
+
+int ttemb_expand_kept(const float* src, const int32_t* map, int64_t nnz, const int32_t* nnz_dev, float* out, void* stream) {
+  ApiRange api_range("ttemb_expand_kept");
+  if (nnz < 0) return fail(TTEMB_E_BADARG, "ttemb_expand_kept: negative size");
+  if (nnz > 0x7fffffffll) return fail(TTEMB_E_BADARG, "ttemb_expand_kept: nnz exceeds int32 range");
+  if (nnz > 0 && (!src || !map || !out)) return fail(TTEMB_E_BADARG, "ttemb_expand_kept: null buffer");
+  if (nnz > 0 && out == src) return fail(TTEMB_E_BADARG, "ttemb_expand_kept: the gather cannot run in place");
+  return launch_expand_kept(src, map, nnz, nnz_dev, out, reinterpret_cast<hipStream_t>(stream));
+}
+
 static int check_cache_args(const void* loc, const void* rowidx, int64_t start, int64_t nnz, int64_t D) {
   if (nnz < 0 || start < 0) return fail(TTEMB_E_BADARG, "negative size");
   if (D <= 0 || D % 4 != 0) return fail(TTEMB_E_BADARG, "embedding_dim %lld must be a positive multiple of 4", (long long)D);

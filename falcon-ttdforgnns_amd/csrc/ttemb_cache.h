@@ -24,6 +24,12 @@ int64_t drop_padding_workspace_bytes(int64_t nnz);
 int launch_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t nnz, int64_t B, int64_t pad,
                         int64_t* indices_out, int64_t* rowidx_out, int64_t* offsets_out, int32_t* nnz_kept_dev, void* ws,
                         int64_t ws_bytes, hipStream_t st);
+// ttemb_compact_bags / ttemb_expand_kept: the same partition behind a device id count, kept part only, weights carried along
+int64_t compact_bags_workspace_bytes(int64_t nnz);
+int launch_compact_bags(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, const int32_t* nnz_dev,
+                        int64_t B, int64_t pad, int64_t* indices_out, int64_t* offsets_out, float* weights_out, int32_t* map_out,
+                        int32_t* kept_dev, void* ws, int64_t ws_bytes, hipStream_t st);
+int launch_expand_kept(const float* src, const int32_t* map, int64_t nnz, const int32_t* nnz_dev, float* out, hipStream_t st);
 int launch_cache_forward(const int32_t* loc, const int64_t* rowidx, const int64_t* offsets, int64_t start,
                          const int32_t* start_dev, int64_t nnz, const float* weight, int64_t D,
                          float* out, hipStream_t st);

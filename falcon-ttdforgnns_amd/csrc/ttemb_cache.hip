@@ -411,6 +411,38 @@ __global__ __launch_bounds__(kPartThreads) void pad_count_kernel(const int64_t* 
   }
 }
 
+// The two halves of "offsets_out[b] = kept ids before clamp(offsets[b])", shared by ttemb_drop_padding and
+// ttemb_compact_bags (`nnz`: what the positions are clamped to).  The first bag whose start lies at position s or later:
+__device__ __forceinline__ int64_t first_bag_from(const int64_t* __restrict__ offsets, int64_t B, int64_t nnz, int64_t s) {
+  int64_t lo = 0, hi = B + 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (clamp_pos(offsets[mid], nnz) < s) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// ... and the words of the bags that start in [s, e), s the tile's first position: from the tile's prefix (`before_block`,
+// `total` kept in the tile) and its four wave ballots, after partition_rank's barrier
+__device__ __forceinline__ void compacted_offsets(const int64_t* __restrict__ offsets, int64_t B, int64_t nnz, int64_t bag_lo,
+                                                  int64_t s, int64_t e, int64_t before_block, int total, const int* wave_cnt,
+                                                  const unsigned long long* wave_ball, int64_t* __restrict__ offsets_out) {
+  for (int64_t b = bag_lo + threadIdx.x; b <= B; b += kPartThreads) {
+    const int64_t p = clamp_pos(offsets[b], nnz);
+    if (p >= e) break;
+    int64_t kb = before_block;
+    const int64_t r = p - s;
+    if (r >= kPartThreads) {
+      kb += total;
+    } else {
+      const int w = (int)(r >> 6);
+      for (int v = 0; v < w; ++v) kb += wave_cnt[v];
+      kb += __popcll(wave_ball[w] & ((1ull << (r & 63)) - 1ull));
+    }
+    offsets_out[b] = kb;
+  }
+}
+
 // offsets_out[b] = kept ids before clamp(offsets[b]): written by the tile that holds that position (the last tile also owns
 // position nnz), from the tile's prefix and its four wave ballots
 __global__ __launch_bounds__(kPartThreads) void pad_scatter_kernel(const int64_t* __restrict__ indices,
@@ -433,14 +465,7 @@ __global__ __launch_bounds__(kPartThreads) void pad_scatter_kernel(const int64_t
       if (n >= first && n < last) row = bag_of_position(offsets, B, n);
     }
     const bool keep = pad_keep(id, n, nnz, first, last, pad);
-    if (threadIdx.x == 0) {   // the first bag whose start lies in this tile or later
-      int64_t lo = 0, hi = B + 1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (clamp_pos(offsets[mid], nnz) < s) lo = mid + 1; else hi = mid;
-      }
-      bag_lo = lo;
-    }
+    if (threadIdx.x == 0) bag_lo = first_bag_from(offsets, B, nnz, s);
     int64_t before_block;
     int total;
     const int64_t before = partition_rank(tilecnt, k, keep, wave_cnt, wave_ball, &before_lds, before_block, total);
@@ -451,21 +476,8 @@ __global__ __launch_bounds__(kPartThreads) void pad_scatter_kernel(const int64_t
       indices_out[dst] = id;
       rowidx_out[dst] = row;
     }
-    const int64_t e = last_tile ? nnz + 1 : s + kPartThreads;
-    for (int64_t b = bag_lo + threadIdx.x; b <= B; b += kPartThreads) {
-      const int64_t p = clamp_pos(offsets[b], nnz);
-      if (p >= e) break;
-      int64_t kb = before_block;
-      const int64_t r = p - s;
-      if (r >= kPartThreads) {
-        kb += total;
-      } else {
-        const int w = (int)(r >> 6);
-        for (int v = 0; v < w; ++v) kb += wave_cnt[v];
-        kb += __popcll(wave_ball[w] & ((1ull << (r & 63)) - 1ull));
-      }
-      offsets_out[b] = kb;
-    }
+    compacted_offsets(offsets, B, nnz, bag_lo, s, last_tile ? nnz + 1 : s + kPartThreads, before_block, total, wave_cnt, wave_ball,
+                      offsets_out);
     __syncthreads();   // (this tile's LDS words are read above; the next tile rewrites them)
   }
 }
@@ -490,6 +502,106 @@ int launch_drop_padding(const int64_t* indices, const int64_t* offsets, int64_t 
   hipLaunchKernelGGL(pad_scatter_kernel, dim3(grid), dim3(kPartThreads), 0, st, indices, offsets, nnz, B, pad, tiles, tilecnt,
                      indices_out, rowidx_out, offsets_out, nnz_kept_dev);
   return check_hip(hipGetLastError(), "pad_scatter_kernel");
+}
+
+// ---------------------------------------------------------------------------------
+// compact bags (ttemb_compact_bags): the partition above as the first node of a captured forward graph.  The live count c
+// comes from a device word (live_count: the launches are sized by the capacity `nnz`, the tiles past c find nothing to do),
+// the keep rule is pad_keep's for nnz = c, the weights ride along, and only the kept part is written -- no tail, no row
+// index: what follows reads indices_out / weights_out up to *kept_dev and offsets_out.  map_out is the way back
+// (ttemb_expand_kept).  Same form: integer and copy work, two launches, no waits between workgroups.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPartThreads) void compact_count_kernel(const int64_t* __restrict__ indices,
+                                                                     const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                     const int32_t* __restrict__ nnz_dev, int64_t B, int64_t pad,
+                                                                     int64_t tiles, int32_t* __restrict__ tilecnt) {
+  const int64_t c = live_count(nnz, nnz_dev);
+  const int64_t first = clamp_pos(offsets[0], c), last = clamp_pos(offsets[B], c);
+  for (int64_t k = blockIdx.x; k < tiles; k += gridDim.x) {   // (every tile's count is written: the scatter sums them)
+    const int64_t n = k * kPartThreads + threadIdx.x;
+    const int64_t id = n < c ? indices[n] : 0;
+    const int cnt = __syncthreads_count(pad_keep(id, n, c, first, last, pad));
+    if (threadIdx.x == 0) tilecnt[k] = cnt;
+  }
+}
+
+__global__ __launch_bounds__(kPartThreads) void compact_scatter_kernel(
+    const int64_t* __restrict__ indices, const int64_t* __restrict__ offsets, const float* __restrict__ weights, int64_t nnz,
+    const int32_t* __restrict__ nnz_dev, int64_t B, int64_t pad, int64_t tiles, const int32_t* __restrict__ tilecnt,
+    int64_t* __restrict__ indices_out, int64_t* __restrict__ offsets_out, float* __restrict__ weights_out,
+    int32_t* __restrict__ map_out, int32_t* __restrict__ kept_dev) {
+  __shared__ int wave_cnt[kPartThreads / kWave];
+  __shared__ unsigned long long wave_ball[kPartThreads / kWave];
+  __shared__ int64_t before_lds, bag_lo;
+  const int64_t c = live_count(nnz, nnz_dev);
+  const int64_t first = clamp_pos(offsets[0], c), last = clamp_pos(offsets[B], c);
+  for (int64_t k = blockIdx.x; k < tiles; k += gridDim.x) {
+    const int64_t s = k * kPartThreads, n = s + threadIdx.x;
+    const bool last_tile = k == tiles - 1;
+    // a tile past position c holds no live id and no bag start (the starts are clamped to c); the last one still has the
+    // kept count to write  (uniform over the workgroup: no barrier is skipped by a part of it)
+    if (s > c && !last_tile) continue;
+    int64_t id = 0;
+    float w = 0.f;
+    if (n < c) {
+      id = indices[n];
+      if (weights != nullptr) w = weights[n];
+    }
+    const bool keep = pad_keep(id, n, c, first, last, pad);
+    if (threadIdx.x == 0) bag_lo = first_bag_from(offsets, B, c, s);
+    int64_t before_block;
+    int total;
+    const int64_t before = partition_rank(tilecnt, k, keep, wave_cnt, wave_ball, &before_lds, before_block, total);
+    if (last_tile && threadIdx.x == 0) *kept_dev = (int32_t)(before_block + total);
+    if (keep) {   // (before < kept <= c: inside the buffers)
+      indices_out[before] = id;
+      if (weights_out != nullptr) weights_out[before] = w;
+    }
+    if (map_out != nullptr && n < c) map_out[n] = keep ? (int32_t)before : -1;
+    // (the last tile also owns position nnz, as in pad_scatter_kernel: c == nnz on a tile edge has no tile of its own)
+    compacted_offsets(offsets, B, c, bag_lo, s, last_tile ? nnz + 1 : s + kPartThreads, before_block, total, wave_cnt, wave_ball,
+                      offsets_out);
+    __syncthreads();   // (this tile's LDS words are read above; the next tile rewrites them)
+  }
+}
+
+int64_t compact_bags_workspace_bytes(int64_t nnz) { return drop_padding_workspace_bytes(nnz); }
+
+int launch_compact_bags(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, const int32_t* nnz_dev,
+                        int64_t B, int64_t pad, int64_t* indices_out, int64_t* offsets_out, float* weights_out, int32_t* map_out,
+                        int32_t* kept_dev, void* ws, int64_t ws_bytes, hipStream_t st) {
+  const int64_t need = compact_bags_workspace_bytes(nnz);
+  if (need > ws_bytes)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_compact_bags needs %lld workspace bytes behind the header, got %lld", (long long)need,
+                (long long)ws_bytes);
+  int32_t* tilecnt = reinterpret_cast<int32_t*>(ws);
+  const int64_t tiles = pad_tiles(nnz);
+  const unsigned grid = exact::ex_grid(tiles);
+  hipLaunchKernelGGL(compact_count_kernel, dim3(grid), dim3(kPartThreads), 0, st, indices, offsets, nnz, nnz_dev, B, pad, tiles,
+                     tilecnt);
+  int rc = check_hip(hipGetLastError(), "compact_count_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(compact_scatter_kernel, dim3(grid), dim3(kPartThreads), 0, st, indices, offsets, weights, nnz, nnz_dev, B, pad,
+                     tiles, tilecnt, indices_out, offsets_out, weights_out, map_out, kept_dev);
+  return check_hip(hipGetLastError(), "compact_scatter_kernel");
+}
+
+// out[n] = src[map[n]], 0 where position n was dropped (ttemb_expand_kept): a gather over the live positions
+__global__ __launch_bounds__(kPartThreads) void expand_kept_kernel(const float* __restrict__ src, const int32_t* __restrict__ map,
+                                                                   int64_t nnz, const int32_t* __restrict__ nnz_dev,
+                                                                   float* __restrict__ out) {
+  const int64_t c = live_count(nnz, nnz_dev);
+  for (int64_t n = (int64_t)blockIdx.x * kPartThreads + threadIdx.x; n < c; n += (int64_t)gridDim.x * kPartThreads) {
+    const int32_t m = map[n];
+    out[n] = m >= 0 && m < nnz ? src[m] : 0.f;   // (m < nnz: a map that was never written cannot send the load astray)
+  }
+}
+
+int launch_expand_kept(const float* src, const int32_t* map, int64_t nnz, const int32_t* nnz_dev, float* out, hipStream_t st) {
+  if (nnz <= 0) return TTEMB_OK;
+  hipLaunchKernelGGL(expand_kept_kernel, dim3(exact::ex_grid(pad_tiles(nnz))), dim3(kPartThreads), 0, st, src, map, nnz, nnz_dev,
+                     out);
+  return check_hip(hipGetLastError(), "expand_kept_kernel");
 }
 
 // ---------------------------------------------------------------------------------

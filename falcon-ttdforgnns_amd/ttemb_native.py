@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
 BAGS_SYMBOLS = ("ttemb_stage_bags", "ttemb_bag_reduce_n", "ttemb_bag_reduce_backward_n", "ttemb_bag_max_n",
                 "ttemb_bag_max_backward_n", "ttemb_pad_weights_n")
 
+# every symbol include/ttemb_pads.h declares (captured padded bags on the partition route; ttemb.h includes that header)
+PADS_SYMBOLS = ("ttemb_compact_bags_workspace_bytes", "ttemb_compact_bags", "ttemb_expand_kept")
 
 
 class Shape(ctypes.Structure):
@@ -232,16 +234,21 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_bag_max_n.argtypes = [vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, i64, vp]
     lib.ttemb_bag_max_backward_n.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp]
     lib.ttemb_pad_weights_n.argtypes = [vp, vp, vp, i64, vp, i64, i64, i32, vp, vp]
+    lib.ttemb_compact_bags_workspace_bytes.restype = i64
+    lib.ttemb_compact_bags_workspace_bytes.argtypes = [i64]
+    lib.ttemb_compact_bags.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.ttemb_expand_kept.argtypes = [vp, vp, i64, vp, vp, vp]
     stp = ctypes.POINTER(StepDesc)
     lib.ttemb_backward_step.argtypes = [shp, vp, vp, vp, vp, i64, vp, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_step_window.argtypes = [shp, vp, vp, vp, i64, i64, i64, i64, vp, stp, vp, i64, vp]
     lib.ttemb_backward_step_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_flat_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, stp, vp, vp]
-    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS + PADS_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
                         "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
-                        "ttemb_drop_padding_workspace_bytes", "ttemb_bag_max_workspace_bytes"):
+                        "ttemb_drop_padding_workspace_bytes", "ttemb_bag_max_workspace_bytes",
+                        "ttemb_compact_bags_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -898,6 +905,55 @@ def pad_weights(indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[
         else:
             _check(LIB.ttemb_pad_weights(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, offsets.numel() - 1, int(pad),
                                          1 if mean else 0, _ptr(weights_out), _stream(weights_out)))
+
+
+def compact_bags_workspace_bytes(nnz: int) -> int:
+    key = ("compact", nnz)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_compact_bags_workspace_bytes(nnz))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def compact_bags(indices: torch.Tensor, offsets: torch.Tensor, weights: Optional[torch.Tensor], pad: int,
+                 indices_out: torch.Tensor, offsets_out: torch.Tensor, weights_out: Optional[torch.Tensor],
+                 map_out: Optional[torch.Tensor], kept_dev: torch.Tensor, ws, nnz_dev: Optional[torch.Tensor] = None) -> None:
+    """``drop_padding`` behind a device id count (``ttemb_compact_bags``): of the first ``c`` positions (``nnz_dev``; None: all)
+    the ids != ``pad`` inside a bag go to ``indices_out[:kept]`` in input order, their ``weights`` (or None) to
+    ``weights_out[:kept]``, the compacted bags to ``offsets_out``, ``kept`` to the int32 word ``kept_dev`` and, with
+    ``map_out`` (int32 ``[nnz]``), every position's compacted place or -1 to ``map_out[:c]``.  Nothing past ``kept`` / ``c`` is
+    written.  ``ws``: a ``Workspace``, or a uint8 tensor of ``compact_bags_workspace_bytes(nnz)``."""
+    nnz, B = indices.numel(), offsets.numel() - 1
+    if (indices.dtype != torch.int64 or offsets.dtype != torch.int64 or indices_out.dtype != torch.int64
+            or offsets_out.dtype != torch.int64 or indices_out.numel() < nnz or offsets_out.numel() != B + 1):
+        raise ValueError("compact_bags: ids and offsets are int64, indices_out holds nnz and offsets_out B + 1 entries")
+    if kept_dev.dtype != torch.int32 or kept_dev.numel() < 1:
+        raise ValueError("compact_bags: kept_dev is an int32 word on the device")
+    if (weights is None) != (weights_out is None):
+        raise ValueError("compact_bags: weights and weights_out come together")
+    _check_sizes((weights, weights_out), nnz)
+    if map_out is not None and (map_out.dtype != torch.int32 or map_out.numel() != nnz):
+        raise ValueError(f"compact_bags: map_out must be int32 [{nnz}]")
+    dev = offsets.device
+    w = ws.get(compact_bags_workspace_bytes(nnz), dev) if isinstance(ws, Workspace) else ws
+    with _on_device(dev):
+        _check(LIB.ttemb_compact_bags(_ptr(indices), _ptr(offsets), _ptr(weights), nnz, _count_word(nnz_dev), B, int(pad),
+                                      _ptr(indices_out), _ptr(offsets_out), _ptr(weights_out), _ptr(map_out), _ptr(kept_dev),
+                                      _ptr(w), w.numel(), _stream(offsets)))
+
+
+def expand_kept(src: torch.Tensor, map_: torch.Tensor, out: torch.Tensor, nnz_dev: Optional[torch.Tensor] = None) -> None:
+    """``out[n] = src[map_[n]]``, 0 where ``map_[n] < 0``, for the first ``c`` positions (``nnz_dev``; None: all); the rest of
+    ``out`` is not touched (``ttemb_expand_kept``: the weight gradient of compacted bags back at the call's positions)."""
+    nnz = map_.numel()
+    _check_sizes((src, out), nnz)
+    if map_.dtype != torch.int32:
+        raise ValueError(f"expand_kept: the map must be int32 [{nnz}]")
+    with _on_device(out.device):
+        _check(LIB.ttemb_expand_kept(_ptr(src), _ptr(map_), nnz, _count_word(nnz_dev), _ptr(out), _stream(out)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

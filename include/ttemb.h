@@ -656,5 +656,6 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
 /* Captured pooled lookups -- the staging launch of a pooled call and the pooling calls that take a device id count -- are
  * declared in ttemb_bags.h, which this header includes: one include serves the whole ABI. */
 #include "ttemb_bags.h"
+#include "ttemb_pads.h"
 
 #endif /* TTEMB_H_ */

@@ -5,13 +5,15 @@ fixed-fanout neighbour table with about 29 % pad ids.
   weighted_2048   the same table with per_sample_weights, mode="sum" (the GCN-weighted aggregation)
   mean_40960      40 960 x 10, mode="mean": the large end
   mean_2048_nopad / weighted_2048_nopad   the 2 048 x 10 workloads on a table without pad ids and a module without
-                  padding_idx, for orientation: a padded captured call always looks every id up (the masked rows of DESIGN
-                  §4.8, where the one hot pad id serialises the lookup), an unpadded one does not
+                  padding_idx, for orientation: a padded captured call on the default route looks every id up (the masked
+                  rows of DESIGN §4.8, where the one hot pad id serialises the lookup), an unpadded one does not
 Legs of each workload:
   eager       emb(table[, per_sample_weights=w]).backward(dy)
   fixed       emb.capture_bags(n, rows, ..., fanout=10): the call of exactly that size
   var_n       ... variable=True at capacity = size: the staging launch and the device count on top of `fixed`
   var_2n      ... variable=True at twice the size: launches sized by twice the live size
+  part_fixed / part_var_n   (padded workloads) `fixed` / `var_n` with pad_route="partition": the pad ids are compacted away by
+              the first node of the forward graph and never reach the TT kernels
 One process; the legs alternate (eager, fixed, var_n, var_2n, eager, ...) in blocks of --steps steps, so they see the same
 clocks.  Per block: host_us = time to enqueue the block / steps (no synchronisation inside a block), wall_us = time until the
 device has finished it / steps.  Reported: the median over --rounds blocks.  The first failure ends the run.
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9, help="blocks per leg")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--eager-only", action="store_true")
+    ap.add_argument("--workloads", default=None, help="comma-separated names (default: all)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     rows, D = int(np.prod(P)), int(np.prod(Q))
@@ -59,7 +62,10 @@ def main():
 
     res = {"device": torch.cuda.get_device_name(0), "steps_per_block": a.steps, "rounds": a.rounds, "fanout": FANOUT,
            "eager_only": a.eager_only, "workloads": {}}
+    picked = None if a.workloads is None else set(a.workloads.split(","))
     for name, n_dst, mode, weighted, padded in WORKLOADS:
+        if picked is not None and name not in picked:
+            continue
         nbr = rng.integers(0, rows - 1, size=(n_dst, FANOUT))
         if padded:
             deg = rng.integers(1, FANOUT + 1, size=n_dst)   # nodes with fewer neighbours than the fanout are filled with the pad
@@ -79,6 +85,11 @@ def main():
             legs["fixed"] = lambda: fixed(table, None, w).backward(dy)
             legs["var_n"] = lambda: var_n(table, None, w).backward(dy)
             legs["var_2n"] = lambda: var_2n(table, None, w).backward(dy)
+            if padded:
+                part_fixed = module(mode, padded).capture_bags(n, n_dst, pad_route="partition", **kw)
+                part_var_n = module(mode, padded).capture_bags(n, n_dst, variable=True, pad_route="partition", **kw)
+                legs["part_fixed"] = lambda: part_fixed(table, None, w).backward(dy)
+                legs["part_var_n"] = lambda: part_var_n(table, None, w).backward(dy)
         for fn in legs.values():
             for _ in range(a.warmup):
                 fn()
@@ -103,6 +114,14 @@ def main():
             out["fixed_vs_eager_wall"] = round(float(np.median(wall["fixed"]) / np.median(wall["eager"])), 3)
             out["var_n_vs_fixed_wall"] = round(float(np.median(wall["var_n"]) / np.median(wall["fixed"])), 3)
             out["var_2n_vs_var_n_wall"] = round(float(np.median(wall["var_2n"]) / np.median(wall["var_n"])), 3)
+            if padded:
+                out["part_fixed_vs_fixed_wall"] = round(float(np.median(wall["part_fixed"]) / np.median(wall["fixed"])), 3)
+                out["part_fixed_vs_eager_wall"] = round(float(np.median(wall["part_fixed"]) / np.median(wall["eager"])), 3)
+                # the static buffers each capture owns (its tensor attributes; a buffer held under two names counts twice):
+                # the masked route's rows / d_rows against the compacted ids
+                held = lambda c: sum(t.numel() * t.element_size() for t in vars(c).values() if isinstance(t, torch.Tensor))
+                out["static_bytes"] = {"fixed": held(fixed), "part_fixed": held(part_fixed)}
+                out["route"] = {"fixed": fixed.route, "part_fixed": part_fixed.route}
         res["workloads"][name] = out
         legs.clear()
     print(json.dumps(res), flush=True)
