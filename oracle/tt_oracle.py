@@ -445,10 +445,14 @@ def tt_forward64(indices, offsets, cores, p_shapes, q_shapes, ranks, weights=Non
     return val, mag
 
 
-def _backward64(ii, rowidx, f, d_output, cores, q, R, absolute):
+def _backward64(ii, rowidx, f, d_output, cores, q, R, absolute, prefix_cores=None):
     T = len(cores)
     n = ii[0].shape[0]
     v, c = _rows64(ii, cores, q, R, absolute)
+    if prefix_cores is not None:   # the saved prefix: v[T-2] alone from the cores the forward ran with
+        assert T >= 2, "a prefix needs at least two cores"
+        v = list(v)
+        v[T - 2] = _rows64(ii[:T - 1], prefix_cores[:T - 1], q, R, absolute)[0][T - 2]
     dy = np.asarray(d_output, dtype=np.float32).astype(np.float64)
     if absolute:
         dy, f = np.abs(dy), np.abs(f)
@@ -465,10 +469,18 @@ def _backward64(ii, rowidx, f, d_output, cores, q, R, absolute):
     return grads, wg
 
 
-def tt_dense_backward64(indices, offsets, d_output, cores, p_shapes, q_shapes, ranks, weights=None, mode="sum", pad=None):
+def tt_dense_backward64(indices, offsets, d_output, cores, p_shapes, q_shapes, ranks, weights=None, mode="sum", pad=None,
+                        prefix_cores=None):
     """Dense core gradients in float64: a list of ``(value, mag, n_ids)`` per core, ``n_ids[i]`` the number of non-pad ids
     (with multiplicity) whose digit in that core is ``i``.  With ``weights``, a second value: ``(value, mag)`` of the
-    weights' gradient (0 for pad ids)."""
+    weights' gradient (0 for pad ids).
+
+    ``prefix_cores``: the cores an earlier forward ran with, for a backward that differentiates the chain at that forward's
+    prefix (a plan's saved P, include/ttemb.h) while the cores have moved on.  The forward partial ``v[T-2]`` -- for three
+    cores ``P = G0[i0].G1[i1]``, the factor dG2 is formed with -- comes from ``prefix_cores``; everything else from
+    ``cores``: ``v[t]`` for ``t < T-2`` and the core rows multiplied on the way down.  ``mag`` follows the same rule on
+    magnitudes.  For a 3-core table only dG2 depends on P: dG1 and dG0 come from ``dP = dY.G2^T``, which no prefix enters.
+    Needs at least two cores (with two, v[0] is the first core's row itself).  ``None`` is today's computation, bit for bit."""
     T = len(p_shapes)
     R = full_ranks(ranks, T)
     q = [int(x) for x in q_shapes]
@@ -479,8 +491,8 @@ def tt_dense_backward64(indices, offsets, d_output, cores, p_shapes, q_shapes, r
         return (out, (np.zeros(0), np.zeros(0))) if weights is not None else out
     rowidx, f, keep = _id_factors(indices, offsets, weights, mode, pad)
     ii = split_index(indices, p_shapes)
-    gv, wv = _backward64(ii, rowidx, f, d_output, cores, q, R, False)
-    gm, wm = _backward64(ii, rowidx, f, d_output, cores, q, R, True)
+    gv, wv = _backward64(ii, rowidx, f, d_output, cores, q, R, False, prefix_cores)
+    gm, wm = _backward64(ii, rowidx, f, d_output, cores, q, R, True, prefix_cores)
     counts = [np.bincount(ii[t][keep], minlength=cores[t].shape[0]).astype(np.int64) for t in range(T)]
     out = list(zip(gv, gm, counts))
     if weights is None:

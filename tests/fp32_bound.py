@@ -51,6 +51,12 @@ groups add nothing beyond the K they are part of.  The table (paths relative to 
 Fused steps are checked from the gradient's bound ``delta = gamma(depth) * mag``: SGD ``w - lr g`` (ttemb_api.hip:647 /
 :695: a product and a difference), Adagrad ``s + g^2``, ``w - lr g / (sqrt(s') + eps)`` (ttemb_api.hip:660-661, :686-690:
 two roundings for s', five for the update: product, root, sum, quotient, difference).
+
+Several calls into one tensor (tests/outstanding.py, test_gpu_outstanding.py): when k backwards add their gradients into
+one ``.grad`` (two lookups through one module, ``retain_graph=True``, a data-parallel bucket filled twice), the expectation
+is the sum of the calls' float64 gradients, ``mag`` the sum of their magnitudes and the depth the largest of the calls'
+depths PLUS ONE PER ACCUMULATION: adding a value within gamma(d) of its own to the tensor is one more rounding of both, and
+gamma(d) + u + gamma(d) u <= gamma(d + 1).
 """
 import numpy as np
 
