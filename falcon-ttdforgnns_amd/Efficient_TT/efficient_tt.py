@@ -10,8 +10,9 @@ registers), so this class is a thin adapter:
 * cores are 2-D ``[p_t, R_t q_t R_{t+1}]`` parameters (no table axis), same row layout as
   ``TTEmbeddingBag`` -- interchangeable after ``squeeze(0)``;
 * ``forward(indices, offsets=None, unique=None, inverse=None) -> [len(indices), D]``: one row
-  per id, no pooling; ``unique`` / ``inverse`` are accepted and unused (no host-side
-  ``torch.unique`` is needed);
+  per id, no pooling; passing ``unique`` and ``inverse`` (or ``dedup=True`` at construction) looks up
+  each distinct id once -- their content is not read, the distinct ids are found on the device
+  (no host-side ``torch.unique`` is needed);
 * backward applies the fused SGD step to the cores with the constructor's ``learning_rate``
   (the reference hard-codes 0.1 at efficient_tt.py:140,159) and hands autograd no gradients.
 
@@ -55,12 +56,58 @@ class TT_core_function(torch.autograd.Function):
         return (None, None) + (None,) * len(m.tt_cores)
 
 
+class TT_dedup_function(torch.autograd.Function):
+    """``TT_core_function`` with each distinct id looked up once: the distinct ids are found on the device
+    (``ttemb_unique_ids``), looked up behind their device count, and ``out[n] = rows[inverse[n]]`` is the mapped pool of bags
+    of one; the backward sums the gradients per distinct id (``ttemb_bag_reduce_mapped_backward``) before the fused SGD step
+    on the distinct ids -- the reference's ``sorted_idx`` / ``sorted_key`` scheme without a host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, module: "Eff_TTEmbedding", indices: torch.Tensor, *tt_cores: torch.Tensor) -> torch.Tensor:
+        n = indices.numel()
+        dev = indices.device
+        _, offsets = module._iota(n, dev)
+        uids = torch.empty_like(indices)
+        inverse = torch.empty(n, dtype=torch.int32, device=dev)
+        perm = torch.empty(n, dtype=torch.int32, device=dev)
+        seg = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        _nat.unique_ids(indices, int(np.prod(module.tt_p_shapes)), uids, inverse, perm, seg, count, module._ws)
+        rows = torch.empty((n, module.embedding_dim), dtype=torch.float32, device=dev)
+        ctx.plan = _nat.new_plan(module._shape, n, dev)
+        _nat.forward(module._shape, _nat.core_views(tt_cores), uids, None, offsets, n, count, n, rows, module._ws, ctx.plan)
+        out = torch.empty_like(rows)
+        _nat.bag_reduce_mapped(rows, inverse, None, offsets, out, module._ws)
+        ctx.module, ctx.uniq = module, (uids, inverse, perm, seg, count, offsets)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output: torch.Tensor):
+        m = ctx.module
+        uids, inverse, perm, seg, count, offsets = ctx.uniq
+        n = uids.numel()
+        g = grad_output.contiguous().float()
+        if g.data_ptr() % 16 != 0:
+            g = g.clone()
+        d_rows = torch.empty_like(g)   # the first `count` rows are written, and read by the step
+        _nat.bag_reduce_mapped_backward(g, None, inverse, perm, seg, count, offsets, d_rows, m._ws)
+        _nat.backward_sgd(m._shape, _nat.core_views(m.tt_cores), uids, None, n, count, n, d_rows, float(m.learning_rate),
+                          m._ws, ctx.plan, offsets)
+        return (None, None) + (None,) * len(m.tt_cores)
+
+
 class Eff_TTEmbedding(torch.nn.Module):
+    """``dedup`` (default False): every call looks up each distinct id once.  A call that passes ``unique`` and ``inverse``
+    (what the reference's callers get from ``torch.unique(indices, sorted=True, return_inverse=True)``) does the same
+    whatever ``dedup`` says -- but the CONTENT of the two tensors is not read: the device pass recomputes exactly that
+    ``torch.unique`` result without a host synchronisation, so a caller may drop its own ``torch.unique``."""
+
     def __init__(self, num_embeddings: int, embedding_dim: int, tt_ranks: List[int],
                  tt_p_shapes: Optional[List[int]] = None, tt_q_shapes: Optional[List[int]] = None,
                  optimizer: str = "SGD", learning_rate: float = 0.1, weight_dist: str = "uniform", device=0,
-                 batch_size: int = 4096) -> None:
+                 batch_size: int = 4096, dedup: bool = False) -> None:
         super().__init__()
+        self.dedup = bool(dedup)
         self.num_embeddings, self.embedding_dim = num_embeddings, embedding_dim
         self.num_tt_core = len(tt_ranks) + 1
         self.tt_ranks = [1] + [int(r) for r in tt_ranks] + [1]
@@ -108,6 +155,12 @@ class Eff_TTEmbedding(torch.nn.Module):
         if not indices.is_cuda:
             raise RuntimeError("Eff_TTEmbedding.forward needs tensors on a ROCm device; there is no CPU fallback")
         indices = indices.long().contiguous()
+        if self.dedup or (unique is not None and inverse is not None):
+            n = indices.numel()
+            if n > (1 << 24) or n * self.embedding_dim * 4 > (1 << 31):
+                raise ValueError(f"Eff_TTEmbedding: dedup of {n} ids is past one row window (2^24 rows or 2 GiB of rows); "
+                                 "split the call or leave unique / inverse out")
+            return TT_dedup_function.apply(self, indices, *self.tt_cores)   # (under no_grad no node is kept, nor its context)
         if not torch.is_grad_enabled():   # inference: no autograd node, no plan kept (ttemb_forward with plan == NULL)
             n = indices.numel()
             _, offs = self._iota(n, indices.device)

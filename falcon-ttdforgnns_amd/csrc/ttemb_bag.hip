@@ -11,6 +11,8 @@
 //              a NaN in a kept position wins over every number (the first NaN position).  Long bags go through the same
 //              fixed chunks as the sums: per chunk the partial (value, position), combined in chunk order by the same
 //              strict rule, so the first position still wins.  The backward sends dOut[b][d] to that position alone.
+//   mapped     reduce over rows[map[i]] (one row per DISTINCT id: the dedup route, include/ttemb_unique.h) with the same
+//              chunks; its backward sums, per distinct id, the gradients of its positions in position order.
 //
 // Every kernel is deterministic by construction, in the sense of the exact-mode contract: no float atomics, no waits
 // between workgroups, grid-stride loops over work items (the grid decides who computes a value, never how), summation
@@ -352,6 +354,243 @@ __global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* 
   }
 }
 
+// ---- pooling through a map (the dedup route: include/ttemb_unique.h) ---------------------------------------
+// The rows buffer holds one row per DISTINCT id ([cap][D]); position n of the id list reads rows[map[n]].  The forward is
+// bag_partial_kernel / bag_reduce_kernel with that indirection (kernels of their own: the ones above are not touched) and the
+// same summation orders, so for equal row bits it gives their bits on the expanded rows.  WEIGHTED = false is a weight of 1
+// without the loads: 1 * r and fma(1, r, a) round as r and r + a.
+__device__ __forceinline__ int64_t clamp_row(int32_t m, int64_t cap) { return m < 0 ? 0 : (m >= cap ? cap - 1 : (int64_t)m); }
+
+// sum_{n in [a, e)} w[n] rows[map[n]][c], n in order (a < e): weighted_sum's order
+template <bool WEIGHTED>
+__device__ __forceinline__ float4 mapped_sum(const float4* __restrict__ rows, int64_t cap, const int32_t* __restrict__ map,
+                                             const float* __restrict__ w, int64_t D4, int64_t c, int64_t a, int64_t e) {
+  float4 acc = rows[clamp_row(map[a], cap) * D4 + c];
+  if constexpr (WEIGHTED) acc = f4_scale(w[a], acc);
+#pragma unroll 8
+  for (int64_t n = a + 1; n < e; ++n) {
+    const float4 r = rows[clamp_row(map[n], cap) * D4 + c];
+    if constexpr (WEIGHTED) acc = f4_fma(w[n], r, acc); else acc = f4_add(r, acc);
+  }
+  return acc;
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBagNT) void bag_partial_mapped_kernel(const float4* __restrict__ rows, int64_t cap,
+                                                                    const int32_t* __restrict__ map, const float* __restrict__ w,
+                                                                    const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                    int64_t D4, int shift, float4* __restrict__ partial) {
+  const int64_t nchunks = chunks_of(nnz);
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
+    const int64_t s = k * kBagChunk, e = s + kBagChunk < nnz ? s + kBagChunk : nnz;
+    const int64_t bs = bag_of_position(offsets, B, s), be = bag_of_position(offsets, B, e - 1);
+    for (int which = 0; which < 2; ++which) {
+      const int64_t b = which == 0 ? bs : be;
+      if (which == 1 && be == bs) break;
+      int64_t n0, n1;
+      bag_range(offsets, nnz, b, n0, n1);
+      const int64_t a = n0 > s ? n0 : s, z = n1 < e ? n1 : e;
+      if (n1 - n0 <= kBagChunk || a >= z) continue;
+      float4* dst = partial + (2 * k + (n0 < s ? 0 : 1)) * D4;
+      for (int64_t c = lane; c < D4; c += W) dst[c] = mapped_sum<WEIGHTED>(rows, cap, map, w, D4, c, a, z);
+    }
+  }
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBagNT) void bag_reduce_mapped_kernel(const float4* __restrict__ rows, int64_t cap,
+                                                                   const int32_t* __restrict__ map, const float* __restrict__ w,
+                                                                   const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                   int64_t D4, int shift, const float4* __restrict__ partial,
+                                                                   float4* __restrict__ out) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
+    int64_t n0, n1;
+    bag_range(offsets, nnz, b, n0, n1);
+    float4* dst = out + b * D4;
+    if (n1 - n0 > kBagChunk) {
+      const int64_t k0 = n0 / kBagChunk, k1 = (n1 - 1) / kBagChunk;
+      for (int64_t c = lane; c < D4; c += W) {
+        float4 acc = partial[(2 * k0 + 1) * D4 + c];
+#pragma unroll 8
+        for (int64_t k = k0 + 1; k <= k1; ++k) acc = f4_add(acc, partial[2 * k * D4 + c]);
+        dst[c] = acc;
+      }
+    } else if (n1 > n0) {
+      for (int64_t c = lane; c < D4; c += W) dst[c] = mapped_sum<WEIGHTED>(rows, cap, map, w, D4, c, n0, n1);
+    } else {
+      for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+  }
+}
+
+// The backward sums, per distinct id j < U, the gradients of its positions: the sorted position list perm (positions by id,
+// equal ids in position order) with the segments seg in the role of the id list with its offsets -- segment j is
+// [seg[j], seg[j + 1]) and its term k is w[perm[k]] dOut[bag(perm[k])], zero for a position outside every bag.
+__device__ __forceinline__ int64_t clamp_to(int64_t p, int64_t hi) { return p < 0 ? 0 : (p > hi ? hi : p); }
+
+// [s0, s1) of segment j, clamped to the sorted list like bag_range
+__device__ __forceinline__ void seg_range(const int64_t* __restrict__ seg, int64_t nnz, int64_t j, int64_t& s0, int64_t& s1) {
+  s0 = clamp_to(seg[j], nnz);
+  s1 = clamp_to(seg[j + 1], nnz);
+  s1 = s1 < s0 ? s0 : s1;
+}
+
+// the segment of sorted position k: the last j < U with seg[j] <= k (seg[0] = 0 <= k)
+__device__ __forceinline__ int64_t seg_of_position(const int64_t* __restrict__ seg, int64_t U, int64_t k) {
+  int64_t lo = 0, hi = U;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (seg[mid] <= k) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// bagidx[n] = the bag of position n, -1 outside every bag: one thread per position, so the binary searches of bag_of_position
+// run side by side ONCE per call instead of one after the other inside every segment sum (the sums then read one word per
+// term).  A workspace array of the call: written here, read by the kernels launched behind it.
+__global__ __launch_bounds__(kBagNT) void position_bags_kernel(const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                               int32_t* __restrict__ bagidx) {
+  const int64_t first = offsets[0], last = offsets[B];
+  for (int64_t n = (int64_t)blockIdx.x * kBagNT + threadIdx.x; n < nnz; n += (int64_t)gridDim.x * kBagNT)
+    bagidx[n] = n >= first && n < last ? (int32_t)bag_of_position(offsets, B, n) : -1;
+}
+
+// term k of the sorted list, column c: the gradient row of its position's bag (zeros outside every bag) and, WEIGHTED, its weight
+template <bool WEIGHTED>
+__device__ __forceinline__ float4 mapped_term(const float4* __restrict__ d_out, const float* __restrict__ w,
+                                              const int32_t* __restrict__ perm, const int32_t* __restrict__ bagidx, int64_t nnz,
+                                              int64_t D4, int64_t c, int64_t k, float& wk) {
+  const int64_t p = clamp_to(perm[k], nnz - 1);
+  if constexpr (WEIGHTED) wk = w[p];
+  const int64_t b = bagidx[p];   // (< B: position_bags_kernel wrote it in this call)
+  if (b >= 0) return d_out[b * D4 + c];
+  return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+// sum of the terms [a, e) in k order (a < e): weighted_sum's rule -- the first term a product, then one fma per term
+template <bool WEIGHTED>
+__device__ __forceinline__ float4 mapped_term_sum(const float4* __restrict__ d_out, const float* __restrict__ w,
+                                                  const int32_t* __restrict__ perm, const int32_t* __restrict__ bagidx,
+                                                  int64_t nnz, int64_t D4, int64_t c, int64_t a, int64_t e) {
+  float wk = 1.0f;
+  float4 acc = mapped_term<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, a, wk);
+  if constexpr (WEIGHTED) acc = f4_scale(wk, acc);
+#pragma unroll 4
+  for (int64_t k = a + 1; k < e; ++k) {
+    const float4 gv = mapped_term<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, k, wk);
+    if constexpr (WEIGHTED) acc = f4_fma(wk, gv, acc); else acc = f4_add(gv, acc);
+  }
+  return acc;
+}
+
+// bag_partial_kernel on the sorted list: the part of every LONG segment (more than kBagChunk positions) that lies in chunk k
+// goes to one of the chunk's two slots.  Chunks at or past seg[U] = the end of the list do not exist.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBagNT) void seg_partial_mapped_kernel(const float4* __restrict__ d_out, const float* __restrict__ w,
+                                                                    const int32_t* __restrict__ perm,
+                                                                    const int64_t* __restrict__ seg,
+                                                                    const int32_t* __restrict__ count_dev,
+                                                                    const int32_t* __restrict__ bagidx, int64_t nnz,
+                                                                    int64_t cap, int64_t D4, int shift,
+                                                                    float4* __restrict__ partial) {
+  const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
+  if (U <= 0) return;
+  const int64_t end = clamp_to(seg[U], nnz);
+  const int64_t nchunks = chunks_of(end);
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
+    const int64_t s = k * kBagChunk, e = s + kBagChunk < end ? s + kBagChunk : end;
+    const int64_t js = seg_of_position(seg, U, s), je = seg_of_position(seg, U, e - 1);
+    for (int which = 0; which < 2; ++which) {
+      const int64_t j = which == 0 ? js : je;
+      if (which == 1 && je == js) break;
+      int64_t s0, s1;
+      seg_range(seg, end, j, s0, s1);
+      const int64_t a = s0 > s ? s0 : s, z = s1 < e ? s1 : e;
+      if (s1 - s0 <= kBagChunk || a >= z) continue;
+      float4* dst = partial + (2 * k + (s0 < s ? 0 : 1)) * D4;
+      for (int64_t c = lane; c < D4; c += W)
+        dst[c] = mapped_term_sum<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, a, z);
+    }
+  }
+}
+
+// d_rows[j], j < U: a short segment one sum in k order, a long one the sum of its chunk partials in chunk order.  One lane
+// group per distinct id; the launch is sized by nnz, the loop stops at U.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kBagNT) void seg_reduce_mapped_kernel(const float4* __restrict__ d_out, const float* __restrict__ w,
+                                                                   const int32_t* __restrict__ perm,
+                                                                   const int64_t* __restrict__ seg,
+                                                                   const int32_t* __restrict__ count_dev,
+                                                                   const int32_t* __restrict__ bagidx, int64_t nnz,
+                                                                   int64_t cap, int64_t D4, int shift,
+                                                                   const float4* __restrict__ partial, float4* __restrict__ d_rows) {
+  const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
+  if (U <= 0) return;
+  const int64_t end = clamp_to(seg[U], nnz);
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  for (int64_t j = (int64_t)blockIdx.x * per_block + g; j < U; j += (int64_t)gridDim.x * per_block) {
+    int64_t s0, s1;
+    seg_range(seg, end, j, s0, s1);
+    float4* dst = d_rows + j * D4;
+    if (s1 - s0 > kBagChunk) {
+      const int64_t k0 = s0 / kBagChunk, k1 = (s1 - 1) / kBagChunk;
+      for (int64_t c = lane; c < D4; c += W) {
+        float4 acc = partial[(2 * k0 + 1) * D4 + c];
+#pragma unroll 8
+        for (int64_t k = k0 + 1; k <= k1; ++k) acc = f4_add(acc, partial[2 * k * D4 + c]);
+        dst[c] = acc;
+      }
+    } else if (s1 > s0) {
+      for (int64_t c = lane; c < D4; c += W)
+        dst[c] = mapped_term_sum<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, s0, s1);
+    } else {
+      for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+  }
+}
+
+// d_w[n] = <dOut[bag(n)], rows[map[n]]>, 0 outside every bag: the dot product and lane butterfly of
+// bag_reduce_backward_kernel, one lane group per position
+__global__ __launch_bounds__(kBagNT) void mapped_weight_grad_kernel(const float4* __restrict__ d_out, const float4* __restrict__ rows,
+                                                                    int64_t cap, const int32_t* __restrict__ map,
+                                                                    const int32_t* __restrict__ bagidx, int64_t nnz,
+                                                                    int64_t D4, int shift, float* __restrict__ d_w) {
+  const int W = 1 << shift;
+  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
+  const int64_t per_block = kBagNT >> shift;
+  const int64_t passes = (D4 + W - 1) >> shift;
+  for (int64_t i = (int64_t)blockIdx.x * per_block + g; i < nnz; i += (int64_t)gridDim.x * per_block) {
+    const int64_t b = bagidx[i];
+    const bool in_bag = b >= 0;
+    const int64_t m = clamp_row(map[i], cap);
+    float dot = 0.0f;
+    for (int64_t k = 0; k < passes; ++k) {   // the same trip count on every lane of the group (the butterfly needs them all)
+      const int64_t c = lane + (k << shift);
+      if (c < D4 && in_bag) {
+        const float4 gv = d_out[b * D4 + c];
+        const float4 r = rows[m * D4 + c];
+        dot = fmaf(gv.x, r.x, dot);
+        dot = fmaf(gv.y, r.y, dot);
+        dot = fmaf(gv.z, r.z, dot);
+        dot = fmaf(gv.w, r.w, dot);
+      }
+    }
+    for (int s = W >> 1; s > 0; s >>= 1) dot += __shfl_xor(dot, s, W);
+    if (lane == 0) d_w[i] = dot;
+  }
+}
+
 unsigned grid_of(int64_t items, const Groups& gr) { return exact::ex_grid((items + gr.per_block - 1) / gr.per_block); }
 
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
@@ -536,6 +775,104 @@ int ttemb_pad_weights_n(const int64_t* indices, const int64_t* offsets, const fl
 int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const float* weights, int64_t nnz, int64_t B,
                       int64_t pad, int32_t mean, float* weights_out, void* stream) {
   return ttemb_pad_weights_n(indices, offsets, weights, nnz, nullptr, B, pad, mean, weights_out, stream);
+}
+
+int ttemb_bag_reduce_mapped(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
+                            int64_t nnz, int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes,
+                            void* stream) {
+  int rc = check_sizes("ttemb_bag_reduce_mapped", nnz, B, D);
+  if (rc) return rc;
+  if (nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: nnz = %lld does not fit the int32 map", (long long)nnz);
+  if (B == 0) return TTEMB_OK;
+  if (offsets == nullptr || output == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: offsets / output is null");
+  if (nnz > 0 && (rows == nullptr || map == nullptr || cap < 1))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: rows / map is null or cap < 1");
+  if (misaligned(rows) || misaligned(output))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: rows / output not 16-byte aligned");
+  const int64_t need = ttemb_bag_workspace_bytes(nnz, B, D);
+  if (workspace_bytes < need || workspace == nullptr)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_reduce_mapped: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
+                (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4, nch = chunks_of(nnz);
+  const Groups gr = groups_of(D4);
+  float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
+  const float4* r4 = reinterpret_cast<const float4*>(rows);
+  float4* o4 = reinterpret_cast<float4*>(output);
+  const bool weighted = weights != nullptr;
+  if (nch > 0) {
+    if (weighted)
+      hipLaunchKernelGGL(bag_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
+                         nnz, B, D4, gr.shift, partial);
+    else
+      hipLaunchKernelGGL(bag_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
+                         nnz, B, D4, gr.shift, partial);
+    if ((rc = check_hip(hipGetLastError(), "bag_partial_mapped_kernel"))) return rc;
+  }
+  if (weighted)
+    hipLaunchKernelGGL(bag_reduce_mapped_kernel<true>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
+                       B, D4, gr.shift, partial, o4);
+  else
+    hipLaunchKernelGGL(bag_reduce_mapped_kernel<false>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
+                       B, D4, gr.shift, partial, o4);
+  return check_hip(hipGetLastError(), "bag_reduce_mapped_kernel");
+}
+
+int ttemb_bag_reduce_mapped_backward(const float* d_output, const float* weights, const float* rows, int64_t cap,
+                                     const int32_t* map, const int32_t* perm, const int64_t* seg, const int32_t* count_dev,
+                                     const int64_t* offsets, int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes("ttemb_bag_reduce_mapped_backward", nnz, B, D);
+  if (rc) return rc;
+  if (nnz > kBagMaxIds)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: nnz = %lld does not fit the int32 map", (long long)nnz);
+  if (nnz == 0) return TTEMB_OK;
+  if (offsets == nullptr || d_rows == nullptr || (B > 0 && d_output == nullptr))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: offsets / d_rows / d_output is null");
+  if (map == nullptr || perm == nullptr || seg == nullptr || count_dev == nullptr || cap < 1)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: map / perm / seg / count_dev is null or cap < 1");
+  if (d_weights != nullptr && rows == nullptr)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: the weight gradient needs the rows");
+  if (misaligned(d_output) || misaligned(rows) || misaligned(d_rows))
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: d_output / rows / d_rows not 16-byte aligned");
+  if (B > kBagMaxIds)
+    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped_backward: B = %lld does not fit the int32 bag index", (long long)B);
+  // behind the chunk partials of ttemb_bag_workspace_bytes: one int32 per position, its bag
+  const int64_t partial_bytes = ttemb_bag_workspace_bytes(nnz, B, D);
+  const int64_t need = partial_bytes + ((nnz * 4 + 255) & ~int64_t(255));
+  if (workspace_bytes < need || workspace == nullptr)
+    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_reduce_mapped_backward: workspace of %lld bytes, need %lld",
+                (long long)workspace_bytes, (long long)need);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int64_t D4 = D / 4, nch = chunks_of(nnz);
+  const Groups gr = groups_of(D4);
+  float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
+  const float4* g4 = reinterpret_cast<const float4*>(d_output);
+  float4* dr4 = reinterpret_cast<float4*>(d_rows);
+  int32_t* bagidx = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(workspace) + partial_bytes);
+  hipLaunchKernelGGL(position_bags_kernel, dim3(exact::ex_grid((nnz + kBagNT - 1) / kBagNT)), dim3(kBagNT), 0, st, offsets, nnz, B,
+                     bagidx);
+  if ((rc = check_hip(hipGetLastError(), "position_bags_kernel"))) return rc;
+  if (weights != nullptr) {
+    hipLaunchKernelGGL(seg_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
+                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial);
+    if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
+    hipLaunchKernelGGL(seg_reduce_mapped_kernel<true>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
+                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial, dr4);
+  } else {
+    hipLaunchKernelGGL(seg_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
+                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial);
+    if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
+    hipLaunchKernelGGL(seg_reduce_mapped_kernel<false>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
+                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial, dr4);
+  }
+  if ((rc = check_hip(hipGetLastError(), "seg_reduce_mapped_kernel"))) return rc;
+  if (d_weights != nullptr) {
+    hipLaunchKernelGGL(mapped_weight_grad_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4,
+                       reinterpret_cast<const float4*>(rows), cap, map, bagidx, nnz, D4, gr.shift, d_weights);
+    rc = check_hip(hipGetLastError(), "mapped_weight_grad_kernel");
+  }
+  return rc;
 }
 
 }  // extern "C"

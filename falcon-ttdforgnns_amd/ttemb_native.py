@@ -51,6 +51,10 @@ BAGS_SYMBOLS = ("ttemb_stage_bags", "ttemb_bag_reduce_n", "ttemb_bag_reduce_back
 # every symbol include/ttemb_pads.h declares (captured padded bags on the partition route; ttemb.h includes that header)
 PADS_SYMBOLS = ("ttemb_compact_bags_workspace_bytes", "ttemb_compact_bags", "ttemb_expand_kept")
 
+# every symbol include/ttemb_unique.h declares (the dedup route of the pooled lookups; ttemb.h includes that header)
+UNIQUE_SYMBOLS = ("ttemb_unique_ids_workspace_bytes", "ttemb_unique_ids", "ttemb_bag_reduce_mapped",
+                  "ttemb_bag_reduce_mapped_backward")
+
 
 class Shape(ctypes.Structure):
     """Mirror of ``ttemb_shape_t``."""
@@ -238,17 +242,22 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_compact_bags_workspace_bytes.argtypes = [i64]
     lib.ttemb_compact_bags.argtypes = [vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.ttemb_expand_kept.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.ttemb_unique_ids_workspace_bytes.restype = i64
+    lib.ttemb_unique_ids_workspace_bytes.argtypes = [i64, i64]
+    lib.ttemb_unique_ids.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_mapped.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_mapped_backward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]
     stp = ctypes.POINTER(StepDesc)
     lib.ttemb_backward_step.argtypes = [shp, vp, vp, vp, vp, i64, vp, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_step_window.argtypes = [shp, vp, vp, vp, i64, i64, i64, i64, vp, stp, vp, i64, vp]
     lib.ttemb_backward_step_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_flat_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, stp, vp, vp]
-    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS + PADS_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS + PADS_SYMBOLS + UNIQUE_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
                         "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
                         "ttemb_drop_padding_workspace_bytes", "ttemb_bag_max_workspace_bytes",
-                        "ttemb_compact_bags_workspace_bytes"):
+                        "ttemb_compact_bags_workspace_bytes", "ttemb_unique_ids_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -954,6 +963,93 @@ def expand_kept(src: torch.Tensor, map_: torch.Tensor, out: torch.Tensor, nnz_de
         raise ValueError(f"expand_kept: the map must be int32 [{nnz}]")
     with _on_device(out.device):
         _check(LIB.ttemb_expand_kept(_ptr(src), _ptr(map_), nnz, _count_word(nnz_dev), _ptr(out), _stream(out)))
+
+
+def unique_ids_workspace_bytes(nnz: int, rows: int) -> int:
+    """Bytes ``unique_ids`` needs (behind the lookups' 40 KB header: the lookups' workspace serves it too)."""
+    key = ("unique", nnz, rows)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_unique_ids_workspace_bytes(nnz, rows))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def unique_ids(indices: torch.Tensor, rows: int, unique_out: torch.Tensor, inverse_out: torch.Tensor, perm_out: torch.Tensor,
+               seg_out: torch.Tensor, count_dev: torch.Tensor, ws) -> None:
+    """The distinct ids of ``indices`` (int64 ``[nnz]``, values in ``[0, rows)``) on the device (``ttemb_unique_ids``): with U
+    their number, ``unique_out[:U]`` (int64) the ids in ascending order, ``inverse_out`` (int32 ``[nnz]``) every position's
+    place in it, ``perm_out`` (int32 ``[nnz]``) the positions sorted by id (stable), ``seg_out[:U + 1]`` (int64 ``[nnz + 1]``)
+    where each id's positions begin in ``perm_out``, U in the int32 word ``count_dev``.  Nothing past U / U + 1 is written.  No
+    host synchronisation.  ``ws``: a ``Workspace``, or a uint8 tensor of ``unique_ids_workspace_bytes(nnz, rows)``."""
+    nnz = indices.numel()
+    if (indices.dtype != torch.int64 or unique_out.dtype != torch.int64 or seg_out.dtype != torch.int64
+            or unique_out.numel() < nnz or seg_out.numel() < nnz + 1):
+        raise ValueError("unique_ids: ids, unique_out and seg_out are int64; unique_out holds nnz and seg_out nnz + 1 entries")
+    for name, t in (("inverse_out", inverse_out), ("perm_out", perm_out)):
+        if t.dtype != torch.int32 or t.numel() < nnz:
+            raise ValueError(f"unique_ids: {name} must be int32 [{nnz}]")
+    if count_dev.dtype != torch.int32 or count_dev.numel() < 1:
+        raise ValueError("unique_ids: count_dev is an int32 word on the device")
+    dev = seg_out.device
+    w = ws.get(unique_ids_workspace_bytes(nnz, int(rows)), dev) if isinstance(ws, Workspace) else ws
+    with _on_device(dev):
+        _check(LIB.ttemb_unique_ids(_ptr(indices), nnz, int(rows), _ptr(unique_out), _ptr(inverse_out), _ptr(perm_out),
+                                    _ptr(seg_out), _ptr(count_dev), _ptr(w), w.numel(), _stream(seg_out)))
+
+
+def _check_map(what: str, t: torch.Tensor, nnz: int, dtype=torch.int32, n: Optional[int] = None) -> None:
+    n = nnz if n is None else n
+    if t.dtype != dtype or t.numel() < n:
+        raise ValueError(f"{what} must be {dtype} with at least {n} elements, got {t.dtype} {list(t.shape)}")
+
+
+def bag_reduce_mapped(rows: torch.Tensor, map_: torch.Tensor, weights: Optional[torch.Tensor], offsets: torch.Tensor,
+                      output: torch.Tensor, ws: Workspace) -> None:
+    """``output[b] = sum_{n in bag b} weights[n] rows[map_[n]]`` (``ttemb_bag_reduce_mapped``; ``weights`` None: 1): rows
+    [cap, D] holds one row per distinct id, ``map_`` (int32 ``[nnz]``) every position's row; output [B, D] fully written."""
+    cap, D = rows.shape
+    nnz, B = map_.numel(), offsets.numel() - 1
+    _check_map("bag_reduce_mapped: the map", map_, nnz)
+    if weights is not None:
+        _check_weights(weights, nnz, rows)
+    _check_sizes((rows,), cap * D)
+    _check_sizes((output,), B * D)
+    dev = output.device
+    w = ws.get(bag_workspace_bytes(nnz, B, D), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_bag_reduce_mapped(_ptr(rows), cap, _ptr(map_), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output),
+                                           _ptr(w), w.numel(), _stream(output)))
+
+
+def bag_reduce_mapped_backward(d_output: torch.Tensor, weights: Optional[torch.Tensor], map_: torch.Tensor, perm: torch.Tensor,
+                               seg: torch.Tensor, count_dev: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor,
+                               ws: Workspace, rows: Optional[torch.Tensor] = None,
+                               d_weights: Optional[torch.Tensor] = None) -> None:
+    """``d_rows[j] = sum_{k in [seg[j], seg[j+1])} weights[perm[k]] d_output[bag(perm[k])]`` for the ``count_dev`` distinct ids
+    (rows past them are neither written nor read), and ``d_weights[n] = <d_output[bag(n)], rows[map_[n]]>`` when ``d_weights``
+    is given (then ``rows`` is needed) (``ttemb_bag_reduce_mapped_backward``).  ``perm`` / ``seg`` / ``count_dev``: what
+    ``unique_ids`` wrote next to ``map_`` (its ``inverse_out``)."""
+    cap, D = d_rows.shape
+    nnz, B = map_.numel(), offsets.numel() - 1
+    _check_map("bag_reduce_mapped_backward: the map", map_, nnz)
+    _check_map("bag_reduce_mapped_backward: perm", perm, nnz)
+    _check_map("bag_reduce_mapped_backward: seg", seg, nnz, torch.int64, nnz + 1)
+    if weights is not None:
+        _check_weights(weights, nnz, d_rows)
+    _check_sizes((d_output,), B * D)
+    _check_sizes((rows,), cap * D)
+    if d_weights is not None:
+        _check_sizes((d_weights,), nnz)
+    dev = d_rows.device
+    # the chunk partials of the pool, and behind them one int32 per position (its bag), rounded up to 256 bytes
+    w = ws.get(bag_workspace_bytes(nnz, B, D) + ((4 * nnz + 255) & ~255), dev)
+    with _on_device(dev):
+        _check(LIB.ttemb_bag_reduce_mapped_backward(_ptr(d_output), _ptr(weights), _ptr(rows), cap, _ptr(map_), _ptr(perm),
+                                                    _ptr(seg), _count_word(count_dev), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                                    _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

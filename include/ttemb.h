@@ -657,5 +657,6 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
  * declared in ttemb_bags.h, which this header includes: one include serves the whole ABI. */
 #include "ttemb_bags.h"
 #include "ttemb_pads.h"
+#include "ttemb_unique.h"
 
 #endif /* TTEMB_H_ */
