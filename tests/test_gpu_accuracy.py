@@ -8,12 +8,10 @@ import pytest
 import torch
 
 import fp32_bound as fb
+from abi_check import EPS, LR, WORST, _abi_run, _check_all, _dev, _inputs, _note, _route
 from oracle import tt_oracle as orc
 
 pytestmark = pytest.mark.gpu
-
-LR, EPS = 0.05, 1e-3
-WORST = {}   # route -> largest err / (u mag) seen (printed at the end of the module)
 
 
 @pytest.fixture(scope="module")
@@ -26,70 +24,6 @@ def nat():
     ttemb_native.set_wide_slab_min_ids(0)
     for k in sorted(WORST):
         print(f"\n  {k:28s} largest err/(u mag) {WORST[k]:.2f}", end="")
-
-
-def _dev(x):
-    return torch.as_tensor(np.ascontiguousarray(x)).cuda()
-
-
-def _note(key, r):
-    WORST[key] = max(WORST.get(key, 0.0), r)
-
-
-def _route(fam, nat):
-    return {nat.FAMILY_SCALAR: "scalar", nat.FAMILY_PER_BAG: "per_bag", nat.FAMILY_PER_BAG_RT: "per_bag",
-            nat.FAMILY_GROUPED: "grouped", nat.FAMILY_GROUPED_WIDE: "wide"}[fam & 7]
-
-
-def _inputs(p, q, R, n_ids, seed, long_bag=600):
-    rng = np.random.default_rng(seed)
-    cores = fb.scaled_cores(rng, p, q, R)
-    ids, offs = fb.skewed_bags(rng, p, n_ids, long_bag)
-    dy = fb.scaled_dy(rng, offs.shape[0] - 1, int(np.prod(q)))
-    st0 = [(rng.random(c.shape) * 1e-6).astype(np.float32) for c in cores]
-    return cores, ids, offs, dy, st0
-
-
-def _check_all(key, route, p, q, R, Rk, cores, ids, offs, dy, st0, out, grads, sgd, ada, ada_st, merged=False, pieces=0):
-    """forward, dense gradients, fused SGD cores, fused Adagrad cores and state against the float64 oracle.  ``R`` is the
-    table's ranks (oracle), ``Rk`` the ranks the kernels ran (padded)."""
-    lens = np.diff(offs)
-    want, mag = orc.tt_forward64(ids, offs, cores, p, q, R)
-    _note(key, fb.assert_fp32_grade(out, want, mag, fb.bag_depth(route, Rk, lens, pieces=pieces), key + " forward", "bag"))
-    ref = orc.tt_dense_backward64(ids, offs, dy, cores, p, q, R)
-    for t, (v, m, n) in enumerate(ref):
-        depth = fb.grad_depth(route, q, Rk, t, n, merged=merged, pieces=pieces)
-        if grads is not None:
-            _note(key, fb.assert_fp32_grade(grads[t], v, m, depth, f"{key} dG{t}", "core row"))
-            fb.assert_untouched(grads[t], np.zeros_like(grads[t]), n, f"{key} dG{t}")
-        delta = fb.gamma(depth) * m
-        if sgd is not None:
-            _note(key, fb.assert_sgd_grade(sgd[t], cores[t], v, delta, LR, f"{key} SGD core {t}"))
-            fb.assert_untouched(sgd[t], cores[t], n, f"{key} SGD core {t}")
-        if ada is not None:
-            _note(key, fb.assert_adagrad_grade(ada[t], ada_st[t], cores[t], st0[t], v, delta, LR, EPS, f"{key} Adagrad core {t}"))
-            fb.assert_untouched(ada[t], cores[t], n, f"{key} Adagrad core {t}")
-            fb.assert_untouched(ada_st[t], st0[t], n, f"{key} Adagrad state {t}")
-
-
-def _abi_run(nat, p, q, R, cores, ids, offs, dy, st0, plan=False):
-    """forward, dense gradients, fused SGD and fused Adagrad through the C ABI (ids with their offsets, no row index)."""
-    shape, ws = nat.make_shape(p, q, R), nat.Workspace()
-    c = [_dev(x) for x in cores]
-    I, O, dY = _dev(ids), _dev(offs), _dev(dy)
-    B, nnz = offs.shape[0] - 1, ids.shape[0]
-    pl = nat.new_plan(shape, nnz, I.device) if plan else None
-    out = torch.full((B, int(np.prod(q))), float("nan"), device="cuda")
-    nat.forward(shape, c, I, None, O, nnz, None, B, out, ws, pl)
-    g = [torch.full_like(x, float("nan")) for x in c]
-    nat.backward_dense(shape, c, I, None, nnz, None, B, dY, g, ws, pl, O)
-    cs = [x.clone() for x in c]
-    nat.backward_sgd(shape, cs, I, None, nnz, None, B, dY, LR, ws, pl, O)
-    ca, st = [x.clone() for x in c], [_dev(s) for s in st0]
-    nat.backward_adagrad(shape, ca, st, I, None, nnz, None, B, dY, LR, EPS, ws, pl, O)
-    torch.cuda.synchronize()
-    h = lambda ts: [x.cpu().numpy() for x in ts]
-    return out.cpu().numpy(), h(g), h(cs), h(ca), h(st)
 
 
 # (key, p, q, inner ranks, ids, path, wanted family without route flags, route flag that must be set or None, kernel ranks)
