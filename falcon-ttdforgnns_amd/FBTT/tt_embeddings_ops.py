@@ -853,6 +853,15 @@ class CapturedBags(CapturedLookup):
     leave cores and state as they are, while Adam -- whose step is dense -- counts a step (``t`` advances, ``m`` and ``v``
     decay), as an eager call of pads only does too.  ``cap.pad_route`` tells which ("partition", "masked", None: no padding).
 
+    ``dedup=True`` (sum and mean bags, outside exact mode, up to 2^20 ids): ``cap.route == "dedup"``.  Behind the compaction
+    of a partitioned capture, the forward graph finds the distinct ids of the (kept) ids on the device
+    (``ttemb_unique_ids_n``: launches and the sort's storage sized by the capacity, the live count read from the count word)
+    into the static ``uids`` / ``inverse`` / ``perm`` / ``seg`` / ``unique_count``, looks ``uids`` up as bags of one into
+    ``rows`` with ``unique_count`` as the count word, and pools through the map (``ttemb_bag_reduce_mapped_n``; a mean
+    without pads divides afterwards).  The backward sums each distinct id's gradient into ``d_rows``
+    (``ttemb_bag_reduce_mapped_backward_n``) and hands it to the lookup's backward on ``uids``.  The sort always runs over the
+    whole capacity: pick one near the usual call.  DESIGN.md §4.16.
+
     ``variable=True``: ``nnz`` and ``B`` are capacities; one launch (``ttemb_stage_bags``) puts ids, offsets (or, with
     ``fanout``, the offsets it generates) and weights into the static buffers and leaves the id count in the device word every
     captured kernel stops at.  ``variable=False``: every call has exactly the captured size.  A call without ids replays the
@@ -861,6 +870,7 @@ class CapturedBags(CapturedLookup):
 
     _MODES = ("sum", "mean", "max")
     _PAD_ROUTES = (None, "masked", "partition")
+    _DEDUP_MAX_IDS = 1 << 20   # up to here the sort of ttemb_unique_ids_n consists of kernels only (include/ttemb_unique_n.h)
 
     @staticmethod
     def check_arguments(module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str], weighted: bool,
@@ -887,15 +897,31 @@ class CapturedBags(CapturedLookup):
             raise ValueError(f"capture_bags(fanout={fanout}): nnz must equal B * fanout, got nnz={nnz}, B={B}")
         return mode
 
+    @staticmethod
+    def check_dedup(nnz: int, mode: str) -> None:
+        """The argument errors of ``capture_bags(dedup=True)``, raised before a device is touched: what the eager dedup route
+        refuses for every module (``_dedup_for``), and what the captured sort adds."""
+        if mode == "max":
+            raise ValueError("dedup with mode='max' is not supported: it needs a max pool that reads its rows through the map "
+                             "and a masked sum per distinct id in the backward.  Use dedup=False for max bags.")
+        if int(nnz) > CapturedBags._DEDUP_MAX_IDS:
+            raise ValueError(f"capture_bags(nnz={nnz}, dedup=True): past 2^20 ids the sort of the distinct-id pass clears its "
+                             "counters with memset nodes when it is captured, which this library keeps out of its graphs.  "
+                             "Capture a smaller capacity, or use dedup=False.")
+
     def __init__(self, module: "TableBatchedTTEmbeddingBag", nnz: int, B: int, mode: Optional[str] = None, weighted: bool = False,
-                 fanout: Optional[int] = None, variable: bool = False, pad_route: Optional[str] = None) -> None:
+                 fanout: Optional[int] = None, variable: bool = False, pad_route: Optional[str] = None,
+                 dedup: bool = False) -> None:
         mode = self.check_arguments(module, nnz, B, mode, weighted, fanout, pad_route)
+        if dedup:
+            self.check_dedup(nnz, mode)
         if module.use_cache and not module.warmup:
             raise RuntimeError("capture_bags() with a live row cache is not supported")
         self.module, self.nnz, self.B = module, int(nnz), int(B)
         self.mode, self.weighted, self.variable = mode, bool(weighted), bool(variable)
         self.fanout = None if fanout is None else int(fanout)
         self.pad = module.padding_idx
+        self.dedup = bool(dedup)
         self._module_mode = module.mode
         self.exact = module._exact_active()   # exact mode: the graphs hold the exact kernels
         if self.variable and self.exact:
@@ -909,14 +935,20 @@ class CapturedBags(CapturedLookup):
                 f"capture_bags(nnz={self.nnz}, B={self.B}, pad_route='partition') is not served in exact mode "
                 "(OptimType.EXACT_SGD / deterministic): the exact kernels take no device id count, and the count of the kept "
                 "ids exists on the device only.  Use pad_route='masked', or a module outside exact mode.")
+        if self.dedup and self.exact:
+            raise RuntimeError(
+                f"capture_bags(nnz={self.nnz}, B={self.B}, dedup=True) is not served in exact mode (OptimType.EXACT_SGD / "
+                "deterministic): the exact kernels take no device id count, and the count of the distinct ids exists on the "
+                "device only.  Use dedup=False, or a module outside exact mode.")
         # how the pads are left out: "partition" (compacted away in front of everything else), "masked" (looked up, weight 0)
         self.pad_route = "partition" if part else ("masked" if self.pad is not None else None)
         mask_pad = None if part else self.pad   # the pad id the pooling kernels have to mask; none once the ids are compacted
         nnz, B, D = self.nnz, self.B, module.embedding_dim
         dev = module.tt_cores[0].device
         f32 = dict(dtype=torch.float32, device=dev)
-        # which route: "plain" (the lookup pools), "mean" (the lookup, then the division), "rows" (bags of one, then the pooling)
-        self.route = "rows" if (mode == "max" or self.weighted or mask_pad is not None) else ("mean" if mode == "mean" else "plain")
+        # which route: "plain" (the lookup pools), "mean" (the lookup, then the division), "rows" (bags of one, then the pooling),
+        # "dedup" (the distinct ids as bags of one, then the pooling through the inverse map)
+        self.route = "dedup" if self.dedup else "rows" if (mode == "max" or self.weighted or mask_pad is not None) else ("mean" if mode == "mean" else "plain")
         self.indices = torch.zeros(nnz, dtype=torch.int64, device=dev)
         # until the first call: one bag that holds every id, the others empty (variable: no id at all)
         self.offsets = torch.full((B + 1,), 0 if self.variable else nnz, dtype=torch.int64, device=dev)
@@ -939,10 +971,20 @@ class CapturedBags(CapturedLookup):
             ids, offs, wts, cnt = self.ids_k, self.offsets_k, self.weights_k, self.kept_dev
         self.output = torch.zeros((B, D), **f32)
         self.d_output = torch.zeros_like(self.output)
-        self.d_sums = torch.zeros_like(self.output) if self.route == "mean" else None
+        # a mean that divides the sums (no padding to mask): the "mean" route, and the dedup route of such a mean
+        div_mean = self.route == "mean" or (self.dedup and mode == "mean" and mask_pad is None)
+        self.d_sums = torch.zeros_like(self.output) if div_mean else None
         self.rows = self.d_rows = self.ones = self.pool_weights = self.argmax = self.d_weights = self.d_weights_out = None
-        if self.route == "rows":
-            # the memory this route costs: two [nnz, D] float32 buffers
+        self.uids = self.inverse = self.perm = self.seg = self.unique_count = self._unique_ws = None
+        if self.dedup:   # what ttemb_unique_ids_n writes with every forward replay, and its private workspace
+            self.uids = torch.zeros(nnz, dtype=torch.int64, device=dev)
+            self.inverse = torch.zeros(nnz, dtype=torch.int32, device=dev)
+            self.perm = torch.zeros(nnz, dtype=torch.int32, device=dev)
+            self.seg = torch.zeros(nnz + 1, dtype=torch.int64, device=dev)
+            self.unique_count = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._unique_ws = torch.zeros(_nat.unique_ids_n_workspace_bytes(nnz, module._table_rows), dtype=torch.uint8, device=dev)
+        if self.route in ("rows", "dedup"):
+            # the memory these routes cost: two [nnz, D] float32 buffers (dedup: the first `unique_count` rows are used)
             self.rows, self.d_rows = torch.zeros((nnz, D), **f32), torch.zeros((nnz, D), **f32)
             self.ones = torch.arange(nnz + 1, dtype=torch.int64, device=dev)   # bags of one; the count word bounds them
             if mode == "max":
@@ -964,32 +1006,45 @@ class CapturedBags(CapturedLookup):
         self._adam_key = module._adam_key()
         ws, shape = self._lean.ws, module._shape
         rows_route = self.route == "rows"
-        # the lookup inside the graphs: (ids, bags, destination) forward, (ids, bags, gradient) backward
-        look_offs, look_B = (self.ones, nnz) if rows_route else (offs, B)
-        look_out = self.rows if rows_route else self.output
-        look_grad = self.d_rows if rows_route else (self.d_sums if self.route == "mean" else self.d_output)
+        # the lookup inside the graphs: (ids, bags, destination) forward, (ids, bags, gradient) backward, its count word
+        # (dedup: the distinct ids as bags of one, behind their count)
+        by_rows = rows_route or self.dedup
+        look_ids, look_cnt = (self.uids, self.unique_count) if self.dedup else (ids, cnt)
+        look_offs, look_B = (self.ones, nnz) if by_rows else (offs, B)
+        look_out = self.rows if by_rows else self.output
+        look_grad = self.d_rows if by_rows else (self.d_sums if self.route == "mean" else self.d_output)
 
         def lookup_forward():
             if self.exact:
-                _nat.forward_exact(shape, _nat.core_ptrs(cores), ids, look_offs, look_B, look_out, ws)
+                _nat.forward_exact(shape, _nat.core_ptrs(cores), look_ids, look_offs, look_B, look_out, ws)
             else:   # (variable: the route is chosen from the capacities, on the host; the kernels read the live count)
-                self.plan = self._lean.forward(cores, ids, look_offs, nnz, look_B, look_out, nnz_dev=cnt)
+                self.plan = self._lean.forward(cores, look_ids, look_offs, nnz, look_B, look_out, nnz_dev=look_cnt)
 
         def lookup_backward():
             if self.exact:
-                _nat.backward_exact(shape, _nat.core_ptrs(cores), ids, look_offs, look_B, look_grad, ws,
+                _nat.backward_exact(shape, _nat.core_ptrs(cores), look_ids, look_offs, look_B, look_grad, ws,
                                     opt_state=None if state is None else _nat.core_ptrs(state), lr=lr, eps=eps,
                                     adam=None if adam is None else (_nat.core_ptrs(adam[0]), adam[1], adam[2]))
             else:
-                self._lean.backward(cores, state, ids, look_offs, nnz, look_B, look_grad, lr, eps, self.plan, adam,
-                                    nnz_dev=cnt)
+                self._lean.backward(cores, state, look_ids, look_offs, nnz, look_B, look_grad, lr, eps, self.plan, adam,
+                                    nnz_dev=look_cnt)
 
         def fwd():
             if part:   # the first node: pads out, kept count into the word every kernel behind it stops at
                 _nat.compact_bags(self.indices, self.offsets, self.weights, self.pad, self.ids_k, self.offsets_k, self.weights_k,
                                   self.map, self.kept_dev, self._pad_ws, nnz_dev=self.nnz_dev)
+            if self.dedup:   # the distinct ids of the (kept) ids, their count into the word the lookup stops at
+                _nat.unique_ids_n(ids, module._table_rows, self.uids, self.inverse, self.perm, self.seg, self.unique_count,
+                                  self._unique_ws, nnz_dev=cnt)
             lookup_forward()
-            if self.route == "mean":
+            if self.dedup:
+                if mask_pad is not None:
+                    _nat.pad_weights(ids, offs, wts, mask_pad, mode == "mean", self.pool_weights, nnz_dev=cnt, counted=True)
+                _nat.bag_reduce_mapped(self.rows, self.inverse, self.pool_weights, offs, self.output, ws, nnz_dev=cnt,
+                                       counted=True)
+                if div_mean:
+                    _nat.bag_mean(self.output, self.output, offs)
+            elif self.route == "mean":
                 _nat.bag_mean(self.output, self.output, offs)
             elif rows_route and mode == "max":
                 _nat.bag_max(self.rows, offs, self.output, self.argmax, ws, None if mask_pad is None else ids,
@@ -999,8 +1054,15 @@ class CapturedBags(CapturedLookup):
                     _nat.pad_weights(ids, offs, wts, mask_pad, mode == "mean", self.pool_weights, nnz_dev=cnt, counted=True)
                 _nat.bag_reduce(self.rows, self.pool_weights, offs, self.output, ws, nnz_dev=cnt, counted=True)
 
-        def bwd():   # (partition: on the compacted buffers the forward replay left)
-            if self.route == "mean":
+        def bwd():   # (partition: on the compacted buffers the forward replay left; dedup: on its map, positions and segments)
+            if self.dedup:
+                if div_mean:
+                    _nat.bag_mean(self.d_output, self.d_sums, offs)
+                _nat.bag_reduce_mapped_backward(self.d_sums if div_mean else self.d_output, self.pool_weights, self.inverse,
+                                                self.perm, self.seg, self.unique_count, offs, self.d_rows, ws,
+                                                rows=self.rows if self.weighted else None, d_weights=self.d_weights,
+                                                nnz_dev=cnt, counted=True)
+            elif self.route == "mean":
                 _nat.bag_mean(self.d_output, self.d_sums, offs)
             elif rows_route and mode == "max":
                 _nat.bag_max_backward(self.d_output, self.argmax, offs, self.d_rows, nnz_dev=cnt, counted=True)
@@ -1008,6 +1070,7 @@ class CapturedBags(CapturedLookup):
                 _nat.bag_reduce_backward(self.d_output, self.pool_weights, offs, self.d_rows, ws,
                                          rows=self.rows if self.weighted else None, d_weights=self.d_weights, nnz_dev=cnt,
                                          counted=True)
+            if by_rows and mode != "max":
                 if self.weighted and mask_pad is not None:
                     _nat.pad_weights(ids, offs, self.d_weights, mask_pad, False, self.d_weights_out, nnz_dev=cnt, counted=True)
                 elif self.weighted and part:   # a pad's weight gradient is exactly 0
@@ -1392,15 +1455,17 @@ class TableBatchedTTEmbeddingBag(nn.Module):
 
     def capture_bags(self, nnz: int, B: int, *, mode: Optional[str] = None, weighted: bool = False,
                      fanout: Optional[int] = None, variable: bool = False,
-                     pad_route: Optional[str] = None) -> CapturedBags:
+                     pad_route: Optional[str] = None, dedup: bool = False) -> CapturedBags:
         """Pooled lookup whose forward and backward replay captured HIP graphs (see ``CapturedBags``): ``mode`` ("sum",
         "mean", "max"; None = the module's), ``weighted`` (every call brings ``per_sample_weights``), the module's
         ``padding_idx``, ``fanout=N`` (2-D ``indices[rows, N]``, ``nnz == B * N``) -- of exactly ``nnz`` ids in ``B`` bags, or,
         with ``variable=True``, of any size up to those capacities.  ``pad_route="partition"`` (a module with
         ``padding_idx``, outside exact mode): the pad ids are dropped on the device as the first node of the forward graph and
-        never reach the TT kernels; None / ``"masked"``: they are looked up and pooled with weight 0."""
+        never reach the TT kernels; None / ``"masked"``: they are looked up and pooled with weight 0.  ``dedup=True`` (sum and
+        mean bags, outside exact mode, up to 2^20 ids): the forward graph finds the distinct ids of every call on the device
+        and the TT kernels look each of them up once (``cap.route == "dedup"``)."""
         self._no_dedup_capture("capture_bags")
-        return CapturedBags(self, nnz, B, mode, weighted, fanout, variable, pad_route)
+        return CapturedBags(self, nnz, B, mode, weighted, fanout, variable, pad_route, dedup)
 
     # ---- lookup -------------------------------------------------------------------
     def _cores(self) -> tuple:

@@ -358,7 +358,8 @@ __global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* 
 // The rows buffer holds one row per DISTINCT id ([cap][D]); position n of the id list reads rows[map[n]].  The forward is
 // bag_partial_kernel / bag_reduce_kernel with that indirection (kernels of their own: the ones above are not touched) and the
 // same summation orders, so for equal row bits it gives their bits on the expanded rows.  WEIGHTED = false is a weight of 1
-// without the loads: 1 * r and fma(1, r, a) round as r and r + a.
+// without the loads: 1 * r and fma(1, r, a) round as r and r + a.  The five kernels take the device id count of the *_n
+// convention above (include/ttemb_unique_n.h): every one uses c = live_count(nnz, nnz_dev) where it would use nnz.
 __device__ __forceinline__ int64_t clamp_row(int32_t m, int64_t cap) { return m < 0 ? 0 : (m >= cap ? cap - 1 : (int64_t)m); }
 
 // sum_{n in [a, e)} w[n] rows[map[n]][c], n in order (a < e): weighted_sum's order
@@ -378,8 +379,10 @@ __device__ __forceinline__ float4 mapped_sum(const float4* __restrict__ rows, in
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kBagNT) void bag_partial_mapped_kernel(const float4* __restrict__ rows, int64_t cap,
                                                                     const int32_t* __restrict__ map, const float* __restrict__ w,
-                                                                    const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                    const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                    const int32_t* __restrict__ nnz_dev, int64_t B,
                                                                     int64_t D4, int shift, float4* __restrict__ partial) {
+  nnz = live_count(nnz, nnz_dev);
   const int64_t nchunks = chunks_of(nnz);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
@@ -403,9 +406,11 @@ __global__ __launch_bounds__(kBagNT) void bag_partial_mapped_kernel(const float4
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kBagNT) void bag_reduce_mapped_kernel(const float4* __restrict__ rows, int64_t cap,
                                                                    const int32_t* __restrict__ map, const float* __restrict__ w,
-                                                                   const int64_t* __restrict__ offsets, int64_t nnz, int64_t B,
+                                                                   const int64_t* __restrict__ offsets, int64_t nnz,
+                                                                   const int32_t* __restrict__ nnz_dev, int64_t B,
                                                                    int64_t D4, int shift, const float4* __restrict__ partial,
                                                                    float4* __restrict__ out) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -497,8 +502,9 @@ __global__ __launch_bounds__(kBagNT) void seg_partial_mapped_kernel(const float4
                                                                     const int64_t* __restrict__ seg,
                                                                     const int32_t* __restrict__ count_dev,
                                                                     const int32_t* __restrict__ bagidx, int64_t nnz,
-                                                                    int64_t cap, int64_t D4, int shift,
-                                                                    float4* __restrict__ partial) {
+                                                                    const int32_t* __restrict__ nnz_dev, int64_t cap,
+                                                                    int64_t D4, int shift, float4* __restrict__ partial) {
+  nnz = live_count(nnz, nnz_dev);
   const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
   if (U <= 0) return;
   const int64_t end = clamp_to(seg[U], nnz);
@@ -531,8 +537,10 @@ __global__ __launch_bounds__(kBagNT) void seg_reduce_mapped_kernel(const float4*
                                                                    const int64_t* __restrict__ seg,
                                                                    const int32_t* __restrict__ count_dev,
                                                                    const int32_t* __restrict__ bagidx, int64_t nnz,
-                                                                   int64_t cap, int64_t D4, int shift,
-                                                                   const float4* __restrict__ partial, float4* __restrict__ d_rows) {
+                                                                   const int32_t* __restrict__ nnz_dev, int64_t cap,
+                                                                   int64_t D4, int shift, const float4* __restrict__ partial,
+                                                                   float4* __restrict__ d_rows) {
+  nnz = live_count(nnz, nnz_dev);
   const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
   if (U <= 0) return;
   const int64_t end = clamp_to(seg[U], nnz);
@@ -565,7 +573,9 @@ __global__ __launch_bounds__(kBagNT) void seg_reduce_mapped_kernel(const float4*
 __global__ __launch_bounds__(kBagNT) void mapped_weight_grad_kernel(const float4* __restrict__ d_out, const float4* __restrict__ rows,
                                                                     int64_t cap, const int32_t* __restrict__ map,
                                                                     const int32_t* __restrict__ bagidx, int64_t nnz,
-                                                                    int64_t D4, int shift, float* __restrict__ d_w) {
+                                                                    const int32_t* __restrict__ nnz_dev, int64_t D4, int shift,
+                                                                    float* __restrict__ d_w) {
+  nnz = live_count(nnz, nnz_dev);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
@@ -777,9 +787,9 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
   return ttemb_pad_weights_n(indices, offsets, weights, nnz, nullptr, B, pad, mean, weights_out, stream);
 }
 
-int ttemb_bag_reduce_mapped(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
-                            int64_t nnz, int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes,
-                            void* stream) {
+int ttemb_bag_reduce_mapped_n(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
+                              int64_t nnz, const int32_t* nnz_dev, int64_t B, int64_t D, float* output, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
   int rc = check_sizes("ttemb_bag_reduce_mapped", nnz, B, D);
   if (rc) return rc;
   if (nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: nnz = %lld does not fit the int32 map", (long long)nnz);
@@ -803,25 +813,31 @@ int ttemb_bag_reduce_mapped(const float* rows, int64_t cap, const int32_t* map, 
   if (nch > 0) {
     if (weighted)
       hipLaunchKernelGGL(bag_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
-                         nnz, B, D4, gr.shift, partial);
+                         nnz, nnz_dev, B, D4, gr.shift, partial);
     else
       hipLaunchKernelGGL(bag_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
-                         nnz, B, D4, gr.shift, partial);
+                         nnz, nnz_dev, B, D4, gr.shift, partial);
     if ((rc = check_hip(hipGetLastError(), "bag_partial_mapped_kernel"))) return rc;
   }
   if (weighted)
     hipLaunchKernelGGL(bag_reduce_mapped_kernel<true>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
-                       B, D4, gr.shift, partial, o4);
+                       nnz_dev, B, D4, gr.shift, partial, o4);
   else
     hipLaunchKernelGGL(bag_reduce_mapped_kernel<false>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
-                       B, D4, gr.shift, partial, o4);
+                       nnz_dev, B, D4, gr.shift, partial, o4);
   return check_hip(hipGetLastError(), "bag_reduce_mapped_kernel");
 }
 
-int ttemb_bag_reduce_mapped_backward(const float* d_output, const float* weights, const float* rows, int64_t cap,
-                                     const int32_t* map, const int32_t* perm, const int64_t* seg, const int32_t* count_dev,
-                                     const int64_t* offsets, int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights,
-                                     void* workspace, int64_t workspace_bytes, void* stream) {
+int ttemb_bag_reduce_mapped(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
+                            int64_t nnz, int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes,
+                            void* stream) {
+  return ttemb_bag_reduce_mapped_n(rows, cap, map, weights, offsets, nnz, nullptr, B, D, output, workspace, workspace_bytes, stream);
+}
+
+int ttemb_bag_reduce_mapped_backward_n(const float* d_output, const float* weights, const float* rows, int64_t cap,
+                                       const int32_t* map, const int32_t* perm, const int64_t* seg, const int32_t* count_dev,
+                                       const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, int64_t D,
+                                       float* d_rows, float* d_weights, void* workspace, int64_t workspace_bytes, void* stream) {
   int rc = check_sizes("ttemb_bag_reduce_mapped_backward", nnz, B, D);
   if (rc) return rc;
   if (nnz > kBagMaxIds)
@@ -855,24 +871,32 @@ int ttemb_bag_reduce_mapped_backward(const float* d_output, const float* weights
   if ((rc = check_hip(hipGetLastError(), "position_bags_kernel"))) return rc;
   if (weights != nullptr) {
     hipLaunchKernelGGL(seg_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial);
+                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial);
     if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
     hipLaunchKernelGGL(seg_reduce_mapped_kernel<true>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial, dr4);
+                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial, dr4);
   } else {
     hipLaunchKernelGGL(seg_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial);
+                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial);
     if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
     hipLaunchKernelGGL(seg_reduce_mapped_kernel<false>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, cap, D4, gr.shift, partial, dr4);
+                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial, dr4);
   }
   if ((rc = check_hip(hipGetLastError(), "seg_reduce_mapped_kernel"))) return rc;
   if (d_weights != nullptr) {
     hipLaunchKernelGGL(mapped_weight_grad_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4,
-                       reinterpret_cast<const float4*>(rows), cap, map, bagidx, nnz, D4, gr.shift, d_weights);
+                       reinterpret_cast<const float4*>(rows), cap, map, bagidx, nnz, nnz_dev, D4, gr.shift, d_weights);
     rc = check_hip(hipGetLastError(), "mapped_weight_grad_kernel");
   }
   return rc;
+}
+
+int ttemb_bag_reduce_mapped_backward(const float* d_output, const float* weights, const float* rows, int64_t cap,
+                                     const int32_t* map, const int32_t* perm, const int64_t* seg, const int32_t* count_dev,
+                                     const int64_t* offsets, int64_t nnz, int64_t B, int64_t D, float* d_rows, float* d_weights,
+                                     void* workspace, int64_t workspace_bytes, void* stream) {
+  return ttemb_bag_reduce_mapped_backward_n(d_output, weights, rows, cap, map, perm, seg, count_dev, offsets, nnz, nullptr, B, D,
+                                            d_rows, d_weights, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

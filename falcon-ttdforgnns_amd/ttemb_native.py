@@ -55,6 +55,10 @@ PADS_SYMBOLS = ("ttemb_compact_bags_workspace_bytes", "ttemb_compact_bags", "tte
 UNIQUE_SYMBOLS = ("ttemb_unique_ids_workspace_bytes", "ttemb_unique_ids", "ttemb_bag_reduce_mapped",
                   "ttemb_bag_reduce_mapped_backward")
 
+# every symbol include/ttemb_unique_n.h declares (the dedup route inside captured graphs; ttemb.h includes that header)
+UNIQUE_N_SYMBOLS = ("ttemb_unique_ids_n_workspace_bytes", "ttemb_unique_ids_n", "ttemb_bag_reduce_mapped_n",
+                    "ttemb_bag_reduce_mapped_backward_n")
+
 
 class Shape(ctypes.Structure):
     """Mirror of ``ttemb_shape_t``."""
@@ -247,17 +251,23 @@ def _load() -> ctypes.CDLL:
     lib.ttemb_unique_ids.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, vp]
     lib.ttemb_bag_reduce_mapped.argtypes = [vp, i64, vp, vp, vp, i64, i64, i64, vp, vp, i64, vp]
     lib.ttemb_bag_reduce_mapped_backward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]
+    lib.ttemb_unique_ids_n_workspace_bytes.restype = i64
+    lib.ttemb_unique_ids_n_workspace_bytes.argtypes = [i64, i64]
+    lib.ttemb_unique_ids_n.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_mapped_n.argtypes = [vp, i64, vp, vp, vp, i64, vp, i64, i64, vp, vp, i64, vp]
+    lib.ttemb_bag_reduce_mapped_backward_n.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, i64, vp]
     stp = ctypes.POINTER(StepDesc)
     lib.ttemb_backward_step.argtypes = [shp, vp, vp, vp, vp, i64, vp, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_backward_step_window.argtypes = [shp, vp, vp, vp, i64, i64, i64, i64, vp, stp, vp, i64, vp]
     lib.ttemb_backward_step_exact.argtypes = [shp, vp, vp, vp, i64, i64, vp, stp, vp, i64, vp, i64, vp]
     lib.ttemb_flat_step.argtypes = [vp, vp, vp, vp, vp, i64, f32, stp, vp, vp]
-    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS + PADS_SYMBOLS + UNIQUE_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + BAGS_SYMBOLS + PADS_SYMBOLS + UNIQUE_SYMBOLS + UNIQUE_N_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("ttemb_last_error", "ttemb_workspace_bytes", "ttemb_plan_bytes", "ttemb_window_workspace_bytes",
                         "ttemb_exact_workspace_bytes", "ttemb_exact_plan_bytes", "ttemb_bag_workspace_bytes",
                         "ttemb_drop_padding_workspace_bytes", "ttemb_bag_max_workspace_bytes",
-                        "ttemb_compact_bags_workspace_bytes", "ttemb_unique_ids_workspace_bytes"):
+                        "ttemb_compact_bags_workspace_bytes", "ttemb_unique_ids_workspace_bytes",
+                        "ttemb_unique_ids_n_workspace_bytes"):
             fn.restype = ctypes.c_int
     return lib
 
@@ -1000,6 +1010,41 @@ def unique_ids(indices: torch.Tensor, rows: int, unique_out: torch.Tensor, inver
                                     _ptr(seg_out), _ptr(count_dev), _ptr(w), w.numel(), _stream(seg_out)))
 
 
+def unique_ids_n_workspace_bytes(nnz_cap: int, rows: int) -> int:
+    """Bytes ``unique_ids_n`` needs for a buffer of ``nnz_cap`` ids (behind the 40 KB header), whatever the live count."""
+    key = ("unique_n", nnz_cap, rows)
+    n = _size_cache.get(key)
+    if n is None:
+        n = int(LIB.ttemb_unique_ids_n_workspace_bytes(nnz_cap, rows))
+        if n < 0:
+            _check(n)
+        n = _size_cache[key] = n
+    return n
+
+
+def unique_ids_n(indices: torch.Tensor, rows: int, unique_out: torch.Tensor, inverse_out: torch.Tensor, perm_out: torch.Tensor,
+                 seg_out: torch.Tensor, count_dev: torch.Tensor, ws, nnz_dev: Optional[torch.Tensor] = None) -> None:
+    """``unique_ids`` of the first ``n`` ids of ``indices`` (``ttemb_unique_ids_n``): ``n`` is read on the device from the
+    int32 word ``nnz_dev`` (None: all), ``indices.numel()`` is the capacity that sizes the launches and the sort's storage.
+    The outputs are those of ``unique_ids(indices[:n], ...)``; nothing past ``U`` / ``n`` / ``U + 1`` is written except
+    ``perm_out[n:]``, and ``indices[n:]`` influences nothing.  Capturable: nothing on the host depends on ``n``.  ``ws``: a
+    ``Workspace``, or a uint8 tensor of ``unique_ids_n_workspace_bytes(nnz_cap, rows)``."""
+    nnz = indices.numel()
+    if (indices.dtype != torch.int64 or unique_out.dtype != torch.int64 or seg_out.dtype != torch.int64
+            or unique_out.numel() < nnz or seg_out.numel() < nnz + 1):
+        raise ValueError("unique_ids_n: ids, unique_out and seg_out are int64; unique_out holds nnz and seg_out nnz + 1 entries")
+    for name, t in (("inverse_out", inverse_out), ("perm_out", perm_out)):
+        if t.dtype != torch.int32 or t.numel() < nnz:
+            raise ValueError(f"unique_ids_n: {name} must be int32 [{nnz}]")
+    if count_dev.dtype != torch.int32 or count_dev.numel() < 1:
+        raise ValueError("unique_ids_n: count_dev is an int32 word on the device")
+    dev = seg_out.device
+    w = ws.get(unique_ids_n_workspace_bytes(nnz, int(rows)), dev) if isinstance(ws, Workspace) else ws
+    with _on_device(dev):
+        _check(LIB.ttemb_unique_ids_n(_ptr(indices), nnz, _count_word(nnz_dev), int(rows), _ptr(unique_out), _ptr(inverse_out),
+                                      _ptr(perm_out), _ptr(seg_out), _ptr(count_dev), _ptr(w), w.numel(), _stream(seg_out)))
+
+
 def _check_map(what: str, t: torch.Tensor, nnz: int, dtype=torch.int32, n: Optional[int] = None) -> None:
     n = nnz if n is None else n
     if t.dtype != dtype or t.numel() < n:
@@ -1007,9 +1052,10 @@ def _check_map(what: str, t: torch.Tensor, nnz: int, dtype=torch.int32, n: Optio
 
 
 def bag_reduce_mapped(rows: torch.Tensor, map_: torch.Tensor, weights: Optional[torch.Tensor], offsets: torch.Tensor,
-                      output: torch.Tensor, ws: Workspace) -> None:
+                      output: torch.Tensor, ws: Workspace, nnz_dev: Optional[torch.Tensor] = None, counted: bool = False) -> None:
     """``output[b] = sum_{n in bag b} weights[n] rows[map_[n]]`` (``ttemb_bag_reduce_mapped``; ``weights`` None: 1): rows
-    [cap, D] holds one row per distinct id, ``map_`` (int32 ``[nnz]``) every position's row; output [B, D] fully written."""
+    [cap, D] holds one row per distinct id, ``map_`` (int32 ``[nnz]``) every position's row; output [B, D] fully written.
+    ``counted`` (here and in the backward): the ``*_n`` entry point, whose kernels stop at the id count in ``nnz_dev``."""
     cap, D = rows.shape
     nnz, B = map_.numel(), offsets.numel() - 1
     _check_map("bag_reduce_mapped: the map", map_, nnz)
@@ -1020,14 +1066,19 @@ def bag_reduce_mapped(rows: torch.Tensor, map_: torch.Tensor, weights: Optional[
     dev = output.device
     w = ws.get(bag_workspace_bytes(nnz, B, D), dev)
     with _on_device(dev):
-        _check(LIB.ttemb_bag_reduce_mapped(_ptr(rows), cap, _ptr(map_), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output),
-                                           _ptr(w), w.numel(), _stream(output)))
+        if counted:
+            _check(LIB.ttemb_bag_reduce_mapped_n(_ptr(rows), cap, _ptr(map_), _ptr(weights), _ptr(offsets), nnz,
+                                                 _count_word(nnz_dev), B, D, _ptr(output), _ptr(w), w.numel(), _stream(output)))
+        else:
+            _check(LIB.ttemb_bag_reduce_mapped(_ptr(rows), cap, _ptr(map_), _ptr(weights), _ptr(offsets), nnz, B, D, _ptr(output),
+                                               _ptr(w), w.numel(), _stream(output)))
 
 
 def bag_reduce_mapped_backward(d_output: torch.Tensor, weights: Optional[torch.Tensor], map_: torch.Tensor, perm: torch.Tensor,
                                seg: torch.Tensor, count_dev: torch.Tensor, offsets: torch.Tensor, d_rows: torch.Tensor,
                                ws: Workspace, rows: Optional[torch.Tensor] = None,
-                               d_weights: Optional[torch.Tensor] = None) -> None:
+                               d_weights: Optional[torch.Tensor] = None, nnz_dev: Optional[torch.Tensor] = None,
+                               counted: bool = False) -> None:
     """``d_rows[j] = sum_{k in [seg[j], seg[j+1])} weights[perm[k]] d_output[bag(perm[k])]`` for the ``count_dev`` distinct ids
     (rows past them are neither written nor read), and ``d_weights[n] = <d_output[bag(n)], rows[map_[n]]>`` when ``d_weights``
     is given (then ``rows`` is needed) (``ttemb_bag_reduce_mapped_backward``).  ``perm`` / ``seg`` / ``count_dev``: what
@@ -1047,9 +1098,15 @@ def bag_reduce_mapped_backward(d_output: torch.Tensor, weights: Optional[torch.T
     # the chunk partials of the pool, and behind them one int32 per position (its bag), rounded up to 256 bytes
     w = ws.get(bag_workspace_bytes(nnz, B, D) + ((4 * nnz + 255) & ~255), dev)
     with _on_device(dev):
-        _check(LIB.ttemb_bag_reduce_mapped_backward(_ptr(d_output), _ptr(weights), _ptr(rows), cap, _ptr(map_), _ptr(perm),
-                                                    _ptr(seg), _count_word(count_dev), _ptr(offsets), nnz, B, D, _ptr(d_rows),
-                                                    _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
+        if counted:
+            _check(LIB.ttemb_bag_reduce_mapped_backward_n(_ptr(d_output), _ptr(weights), _ptr(rows), cap, _ptr(map_), _ptr(perm),
+                                                          _ptr(seg), _count_word(count_dev), _ptr(offsets), nnz,
+                                                          _count_word(nnz_dev), B, D, _ptr(d_rows), _ptr(d_weights), _ptr(w),
+                                                          w.numel(), _stream(d_rows)))
+        else:
+            _check(LIB.ttemb_bag_reduce_mapped_backward(_ptr(d_output), _ptr(weights), _ptr(rows), cap, _ptr(map_), _ptr(perm),
+                                                        _ptr(seg), _count_word(count_dev), _ptr(offsets), nnz, B, D, _ptr(d_rows),
+                                                        _ptr(d_weights), _ptr(w), w.numel(), _stream(d_rows)))
 
 
 def cache_update(indices: torch.Tensor, hashtbl: torch.Tensor, cache_freq: torch.Tensor, one_sweep: bool = False) -> None:

@@ -658,5 +658,6 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
 #include "ttemb_bags.h"
 #include "ttemb_pads.h"
 #include "ttemb_unique.h"
+#include "ttemb_unique_n.h"
 
 #endif /* TTEMB_H_ */

@@ -17,9 +17,18 @@ Legs of each workload:
 One process; the legs alternate (eager, fixed, var_n, var_2n, eager, ...) in blocks of --steps steps, so they see the same
 clocks.  Per block: host_us = time to enqueue the block / steps (no synchronisation inside a block), wall_us = time until the
 device has finished it / steps.  Reported: the median over --rounds blocks.  The first failure ends the run.
+--dedup measures the captured dedup route instead (capture_bags(..., dedup=True)): unpadded neighbour blocks
+of 2 048 x 10 and 40 960 x 10 ids, mode="mean" and weighted mode="sum", whose ids are a permutation (100 % distinct) or drawn
+from a pool of nnz / 4 or nnz / 16 values (about 25 % / 6 % distinct: the generators of tools/dedup_bench.py).  Legs:
+  cap_plain     emb.capture_bags(n, rows, ..., fanout=10): today's captured route
+  cap_dedup     ... dedup=True
+  cap_dedup_2n  ... dedup=True, variable=True at twice the size: the sort runs over the whole capacity
+  eager_dedup   emb(table[, per_sample_weights=w], dedup=True).backward(dy)
+A checkout whose capture_bags has no `dedup` keyword (the parent commit) runs cap_plain and eager_dedup alone.
 --eager-only times the eager leg alone and needs nothing of capture_bags: copied into a checkout of the parent commit it
 gives that commit's numbers, the baseline, from the same session.  Prints one JSON line; --out writes it as a JSON file."""
 import argparse
+import inspect
 import json
 import os
 import sys
@@ -36,9 +45,85 @@ from FBTT.tt_embeddings_ops import OptimType, TTEmbeddingBag  # noqa: E402
 P, Q, R = [125, 140, 140], [4, 5, 5], [16, 16]
 FANOUT = 10
 # (name, destinations, mode, weighted, padded)
+DEDUP_SIZES = (2_048, 40_960)
+DEDUP_MODES = (("mean", "mean", False), ("weighted", "sum", True))   # (name, mode, weighted)
+DEDUP_POOLS = ((0, "distinct_100"), (4, "distinct_25"), (16, "distinct_6"))   # (pool of nnz / k values, name)
 WORKLOADS = (("mean_2048", 2_048, "mean", False, True), ("weighted_2048", 2_048, "sum", True, True),
              ("mean_40960", 40_960, "mean", False, True), ("mean_2048_nopad", 2_048, "mean", False, False),
              ("weighted_2048_nopad", 2_048, "sum", True, False))
+
+
+def _measure(legs, a):
+    """Median host and wall microseconds per step of every leg; the legs alternate in blocks of --steps steps."""
+    for fn in legs.values():
+        for _ in range(a.warmup):
+            fn()
+    torch.cuda.synchronize()
+    host = {k: [] for k in legs}
+    wall = {k: [] for k in legs}
+    for _ in range(a.rounds):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            t2 = time.perf_counter()
+            host[k].append((t1 - t0) / a.steps * 1e6)
+            wall[k].append((t2 - t0) / a.steps * 1e6)
+    med = lambda v: round(float(np.median(v)), 1)
+    spread = lambda v: [round(float(min(v)), 1), round(float(max(v)), 1)]
+    return ({k: med(v) for k, v in wall.items()}, {k: med(v) for k, v in host.items()}, {k: spread(v) for k, v in wall.items()})
+
+
+def dedup_main(a):
+    from dedup_bench import pool_ids
+    rows, D = int(np.prod(P)), int(np.prod(Q))
+    dev = "cuda"
+    rng = np.random.default_rng(0)
+    has_dedup = "dedup" in inspect.signature(TTEmbeddingBag.capture_bags).parameters
+
+    def module(mode):
+        torch.manual_seed(0)
+        return TTEmbeddingBag(rows, D, R, P, Q, optimizer=OptimType.SGD, learning_rate=1e-6, use_cache=False, weight_dist="normal",
+                              mode=mode)
+
+    res = {"device": torch.cuda.get_device_name(0), "steps_per_block": a.steps, "rounds": a.rounds, "fanout": FANOUT,
+           "captured_dedup": has_dedup, "workloads": {}}
+    picked = None if a.workloads is None else set(a.workloads.split(","))
+    for n_dst in DEDUP_SIZES:
+        n = n_dst * FANOUT
+        for mname, mode, weighted in DEDUP_MODES:
+            if picked is not None and f"{mname}_{n_dst}" not in picked:
+                continue
+            kw = dict(mode=mode, weighted=weighted, fanout=FANOUT)
+            eager = module(mode)
+            plain = module(mode).capture_bags(n, n_dst, **kw)
+            dedup = module(mode).capture_bags(n, n_dst, dedup=True, **kw) if has_dedup else None
+            dedup_2n = module(mode).capture_bags(2 * n, 2 * n_dst, dedup=True, variable=True, **kw) if has_dedup else None
+            w = torch.rand(n_dst, FANOUT, device=dev) if weighted else None
+            dy = torch.randn(n_dst, D, device=dev) * 1e-3
+            for pool, level in DEDUP_POOLS:
+                ids_np = pool_ids(rng, rows, n, pool)
+                table = torch.as_tensor(ids_np.astype(np.int64)).to(dev).view(n_dst, FANOUT)
+                legs = {"cap_plain": lambda: plain(table, None, w).backward(dy)}
+                if has_dedup:
+                    legs["cap_dedup"] = lambda: dedup(table, None, w).backward(dy)
+                    legs["cap_dedup_2n"] = lambda: dedup_2n(table, None, w).backward(dy)
+                legs["eager_dedup"] = lambda: eager(table, per_sample_weights=w, dedup=True).backward(dy)
+                wall, host, spread = _measure(legs, a)
+                out = {"destinations": n_dst, "ids": n, "mode": mode, "weighted": weighted,
+                       "distinct_fraction": round(np.unique(ids_np).shape[0] / n, 4), "wall_us": wall, "host_us": host,
+                       "wall_us_min_max": spread}
+                if has_dedup:
+                    out["cap_dedup_vs_cap_plain_wall"] = round(wall["cap_dedup"] / wall["cap_plain"], 3)
+                    out["cap_dedup_vs_eager_dedup_wall"] = round(wall["cap_dedup"] / wall["eager_dedup"], 3)
+                res["workloads"][f"{mname}_{n_dst}/{level}"] = out
+                print(f"# {mname}_{n_dst}/{level}: wall {wall} host {host}", file=sys.stderr, flush=True)
+    print(json.dumps(res), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
 
 
 def main():
@@ -47,9 +132,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=9, help="blocks per leg")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--eager-only", action="store_true")
+    ap.add_argument("--dedup", action="store_true", help="the captured dedup route against the captured plain route and eager dedup")
     ap.add_argument("--workloads", default=None, help="comma-separated names (default: all)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.dedup:
+        return dedup_main(a)
     rows, D = int(np.prod(P)), int(np.prod(Q))
     pad = rows - 1
     dev = "cuda"
@@ -90,33 +178,17 @@ def main():
                 part_var_n = module(mode, padded).capture_bags(n, n_dst, variable=True, pad_route="partition", **kw)
                 legs["part_fixed"] = lambda: part_fixed(table, None, w).backward(dy)
                 legs["part_var_n"] = lambda: part_var_n(table, None, w).backward(dy)
-        for fn in legs.values():
-            for _ in range(a.warmup):
-                fn()
-        torch.cuda.synchronize()
-        host = {k: [] for k in legs}
-        wall = {k: [] for k in legs}
-        for _ in range(a.rounds):
-            for k, fn in legs.items():
-                t0 = time.perf_counter()
-                for _ in range(a.steps):
-                    fn()
-                t1 = time.perf_counter()
-                torch.cuda.synchronize()
-                t2 = time.perf_counter()
-                host[k].append((t1 - t0) / a.steps * 1e6)
-                wall[k].append((t2 - t0) / a.steps * 1e6)
-        med = lambda v: round(float(np.median(v)), 1)
+        wall, host, _ = _measure(legs, a)
         out = {"destinations": n_dst, "ids": n, "pad_share": round(float((nbr == pad).mean()), 3), "mode": mode,
                "weighted": weighted, "eager_pad_route": eager._last_pad_route if padded else None,
-               "wall_us": {k: med(v) for k, v in wall.items()}, "host_us": {k: med(v) for k, v in host.items()}}
+               "wall_us": wall, "host_us": host}
         if not a.eager_only:
-            out["fixed_vs_eager_wall"] = round(float(np.median(wall["fixed"]) / np.median(wall["eager"])), 3)
-            out["var_n_vs_fixed_wall"] = round(float(np.median(wall["var_n"]) / np.median(wall["fixed"])), 3)
-            out["var_2n_vs_var_n_wall"] = round(float(np.median(wall["var_2n"]) / np.median(wall["var_n"])), 3)
+            out["fixed_vs_eager_wall"] = round(wall["fixed"] / wall["eager"], 3)
+            out["var_n_vs_fixed_wall"] = round(wall["var_n"] / wall["fixed"], 3)
+            out["var_2n_vs_var_n_wall"] = round(wall["var_2n"] / wall["var_n"], 3)
             if padded:
-                out["part_fixed_vs_fixed_wall"] = round(float(np.median(wall["part_fixed"]) / np.median(wall["fixed"])), 3)
-                out["part_fixed_vs_eager_wall"] = round(float(np.median(wall["part_fixed"]) / np.median(wall["eager"])), 3)
+                out["part_fixed_vs_fixed_wall"] = round(wall["part_fixed"] / wall["fixed"], 3)
+                out["part_fixed_vs_eager_wall"] = round(wall["part_fixed"] / wall["eager"], 3)
                 # the static buffers each capture owns (its tensor attributes; a buffer held under two names counts twice):
                 # the masked route's rows / d_rows against the compacted ids
                 held = lambda c: sum(t.numel() * t.element_size() for t in vars(c).values() if isinstance(t, torch.Tensor))

@@ -26,6 +26,14 @@ N_DST, FANOUT = 40_960, 10
 POOLS = (0, 2, 4, 16)   # 0: a permutation; k: drawn from nnz / k values
 
 
+def pool_ids(rng, rows, nnz, pool):
+    """``nnz`` ids of a table of ``rows``: a permutation (``pool == 0``: every id distinct) or drawn uniformly from a pool of
+    ``nnz // pool`` values.  Also the generator of ``tools/capture_bags_bench.py --dedup``."""
+    if pool == 0:
+        return rng.permutation(rows)[:nnz]
+    return rng.choice(rows, nnz // pool, replace=False)[rng.integers(0, nnz // pool, size=nnz)]
+
+
 def _timed(fn):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -54,10 +62,7 @@ def main():
 
     cases, frac = {}, {}
     for pool in POOLS:
-        if pool == 0:
-            ids_np = rng.permutation(rows)[:nnz]
-        else:
-            ids_np = rng.choice(rows, nnz // pool, replace=False)[rng.integers(0, nnz // pool, size=nnz)]
+        ids_np = pool_ids(rng, rows, nnz, pool)
         level = "distinct" if pool == 0 else f"pool_nnz/{pool}"
         frac[level] = np.unique(ids_np).shape[0] / nnz
         ids = torch.as_tensor(ids_np.astype(np.int64)).to(dev)
