@@ -14,6 +14,10 @@
 //   mapped     reduce over rows[map[i]] (one row per DISTINCT id: the dedup route, include/ttemb_unique.h) with the same
 //              chunks; its backward sums, per distinct id, the gradients of its positions in position order.
 //
+// The three sums (reduce, mapped reduce, the mapped backward) are one chunked segment sum: chunk_partials / segment_sums
+// below hold the chunks, the two slots per chunk and the chunk order once, and the kernels are wrappers that say what the
+// segments and the terms are.  The max kernels have another combine rule and carry positions: they stand apart.
+//
 // Every kernel is deterministic by construction, in the sense of the exact-mode contract: no float atomics, no waits
 // between workgroups, grid-stride loops over work items (the grid decides who computes a value, never how), summation
 // orders set by `offsets` (and D) alone, and every workspace word that is read was written earlier in the same call.
@@ -66,58 +70,72 @@ __device__ __forceinline__ void bag_range(const int64_t* __restrict__ offsets, i
   n1 = n1 < n0 ? n0 : (n1 > nnz ? nnz : n1);
 }
 
-// sum_{i in [a, e)} w[i] rows[i][c], i in order (a < e): the first term a product, then one fma per id
-__device__ __forceinline__ float4 weighted_sum(const float4* __restrict__ rows, const float* __restrict__ w, int64_t D4,
-                                               int64_t c, int64_t a, int64_t e) {
-  float4 acc = f4_scale(w[a], rows[a * D4 + c]);
-#pragma unroll 8
-  for (int64_t i = a + 1; i < e; ++i) acc = f4_fma(w[i], rows[i * D4 + c], acc);
-  return acc;
-}
+// ---- the chunked segment sum ---------------------------------------------------------------------------------------------------
+// A position list cut into segments, one sum of terms per segment and column.  Written once, over two answers:
+//   Segs    `end` positions in `count` segments; of(n) = the segment that holds position n, range(j) = [n0, n1) of segment j,
+//           clamped to the list.  BagSegs: the id list in bags; SortedSegs: the sorted list in runs of one distinct id.
+//   Terms   sum(D4, c, a, e) = the sum of the terms [a, e) of column c, in order (a < e): the first term a product (or a plain
+//           load), every later term one fma (or one add).  RowTerms, MappedTerms, GradTerms below.
+// The chunks, the two slots per chunk and the order in which partials are added are the same for every pair, so equal
+// terms give equal bits whichever pair summed them.
+struct BagSegs {
+  const int64_t* __restrict__ offsets;
+  int64_t count, end;   // B and the live id count
+  __device__ __forceinline__ int64_t of(int64_t n) const { return bag_of_position(offsets, count, n); }
+  __device__ __forceinline__ void range(int64_t b, int64_t& n0, int64_t& n1) const { bag_range(offsets, end, b, n0, n1); }
+};
 
-// Chunk k = positions [k C, (k+1) C): the part of every LONG bag (more than C ids) that lies in it goes to one of the
-// chunk's two slots -- slot 0 for the bag that began before the chunk, slot 1 for the bag that begins inside it (a long bag
-// cannot lie wholly inside a chunk, so there are at most these two).  Short bags are summed by bag_reduce_kernel.
-__global__ __launch_bounds__(kBagNT) void bag_partial_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
-                                                             const int64_t* __restrict__ offsets, int64_t nnz,
-                                                             const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
-                                                             int shift, float4* __restrict__ partial) {
-  nnz = live_count(nnz, nnz_dev);
-  const int64_t nchunks = chunks_of(nnz);
+// terms w[i] rows[i][c]
+struct RowTerms {
+  const float4* __restrict__ rows;
+  const float* __restrict__ w;
+  __device__ __forceinline__ float4 sum(int64_t D4, int64_t c, int64_t a, int64_t e) const {
+    float4 acc = f4_scale(w[a], rows[a * D4 + c]);
+#pragma unroll 8
+    for (int64_t i = a + 1; i < e; ++i) acc = f4_fma(w[i], rows[i * D4 + c], acc);
+    return acc;
+  }
+};
+
+// Chunk k = positions [k C, (k+1) C): the part of every LONG segment (more than C positions) that lies in it goes to one of
+// the chunk's two slots -- slot 0 for the segment that began before the chunk, slot 1 for the segment that begins inside it (a
+// long segment cannot lie wholly inside a chunk, so there are at most these two).  Short segments are summed by segment_sums.
+template <class Segs, class Terms>
+__device__ __forceinline__ void chunk_partials(const Segs segs, const Terms terms, int64_t D4, int shift,
+                                               float4* __restrict__ partial) {
+  const int64_t end = segs.end, nchunks = chunks_of(end);
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
   for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
-    const int64_t s = k * kBagChunk, e = s + kBagChunk < nnz ? s + kBagChunk : nnz;
-    const int64_t bs = bag_of_position(offsets, B, s), be = bag_of_position(offsets, B, e - 1);
+    const int64_t s = k * kBagChunk, e = s + kBagChunk < end ? s + kBagChunk : end;
+    const int64_t js = segs.of(s), je = segs.of(e - 1);
     for (int which = 0; which < 2; ++which) {
-      const int64_t b = which == 0 ? bs : be;
-      if (which == 1 && be == bs) break;
+      const int64_t j = which == 0 ? js : je;
+      if (which == 1 && je == js) break;
       int64_t n0, n1;
-      bag_range(offsets, nnz, b, n0, n1);
+      segs.range(j, n0, n1);
       const int64_t a = n0 > s ? n0 : s, z = n1 < e ? n1 : e;
       if (n1 - n0 <= kBagChunk || a >= z) continue;
       float4* dst = partial + (2 * k + (n0 < s ? 0 : 1)) * D4;
-      for (int64_t c = lane; c < D4; c += W) dst[c] = weighted_sum(rows, w, D4, c, a, z);
+      for (int64_t c = lane; c < D4; c += W) dst[c] = terms.sum(D4, c, a, z);
     }
   }
 }
 
-// out[b]: a bag of one id is a scale and a store; a short bag one sum in position order; a long bag the sum of its chunk
-// partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); an empty bag zeros.
-__global__ __launch_bounds__(kBagNT) void bag_reduce_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
-                                                            const int64_t* __restrict__ offsets, int64_t nnz,
-                                                            const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
-                                                            int shift, const float4* __restrict__ partial,
-                                                            float4* __restrict__ out) {
-  nnz = live_count(nnz, nnz_dev);
+// out[j], j < count: a short segment is one sum in position order (a segment of one term a scale and a store); a long one the
+// sum of its chunk partials in chunk order (its first chunk's slot 1, then slot 0 of every later chunk it reaches); an empty
+// one zeros.  One lane group per segment.
+template <class Segs, class Terms>
+__device__ __forceinline__ void segment_sums(const Segs segs, const Terms terms, int64_t D4, int shift,
+                                             const float4* __restrict__ partial, float4* __restrict__ out) {
   const int W = 1 << shift;
   const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
   const int64_t per_block = kBagNT >> shift;
-  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
+  for (int64_t j = (int64_t)blockIdx.x * per_block + g; j < segs.count; j += (int64_t)gridDim.x * per_block) {
     int64_t n0, n1;
-    bag_range(offsets, nnz, b, n0, n1);
-    float4* dst = out + b * D4;
+    segs.range(j, n0, n1);
+    float4* dst = out + j * D4;
     if (n1 - n0 > kBagChunk) {
       const int64_t k0 = n0 / kBagChunk, k1 = (n1 - 1) / kBagChunk;
       for (int64_t c = lane; c < D4; c += W) {
@@ -127,11 +145,41 @@ __global__ __launch_bounds__(kBagNT) void bag_reduce_kernel(const float4* __rest
         dst[c] = acc;
       }
     } else if (n1 > n0) {
-      for (int64_t c = lane; c < D4; c += W) dst[c] = weighted_sum(rows, w, D4, c, n0, n1);
+      for (int64_t c = lane; c < D4; c += W) dst[c] = terms.sum(D4, c, n0, n1);
     } else {
       for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
   }
+}
+
+// out[b] = sum_{i in bag b} w[i] rows[i]: the chunk partials of the long bags, then every bag
+__global__ __launch_bounds__(kBagNT) void bag_partial_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
+                                                             const int64_t* __restrict__ offsets, int64_t nnz,
+                                                             const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                             int shift, float4* __restrict__ partial) {
+  chunk_partials(BagSegs{offsets, B, live_count(nnz, nnz_dev)}, RowTerms{rows, w}, D4, shift, partial);
+}
+
+__global__ __launch_bounds__(kBagNT) void bag_reduce_kernel(const float4* __restrict__ rows, const float* __restrict__ w,
+                                                            const int64_t* __restrict__ offsets, int64_t nnz,
+                                                            const int32_t* __restrict__ nnz_dev, int64_t B, int64_t D4,
+                                                            int shift, const float4* __restrict__ partial,
+                                                            float4* __restrict__ out) {
+  segment_sums(BagSegs{offsets, B, live_count(nnz, nnz_dev)}, RowTerms{rows, w}, D4, shift, partial, out);
+}
+
+// dot + <g, r>, x to w in order
+__device__ __forceinline__ float dot4(float4 g, float4 r, float dot) {
+  dot = fmaf(g.x, r.x, dot);
+  dot = fmaf(g.y, r.y, dot);
+  dot = fmaf(g.z, r.z, dot);
+  return fmaf(g.w, r.w, dot);
+}
+
+// the sum of v over the W lanes of a group, on every lane: a butterfly, a fixed tree for a given W
+__device__ __forceinline__ float group_sum(float v, int W) {
+  for (int m = W >> 1; m > 0; m >>= 1) v += __shfl_xor(v, m, W);
+  return v;
 }
 
 // d_rows[i] = w[i] dOut[bag(i)]; d_w[i] = <dOut[bag(i)], rows[i]> (each lane sums its columns in order, then a butterfly
@@ -159,17 +207,11 @@ __global__ __launch_bounds__(kBagNT) void bag_reduce_backward_kernel(const float
       if (c < D4) {
         const float4 gv = in_bag ? d_out[b * D4 + c] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         d_rows[i * D4 + c] = f4_scale(wi, gv);
-        if (d_w != nullptr) {
-          const float4 r = rows[i * D4 + c];
-          dot = fmaf(gv.x, r.x, dot);
-          dot = fmaf(gv.y, r.y, dot);
-          dot = fmaf(gv.z, r.z, dot);
-          dot = fmaf(gv.w, r.w, dot);
-        }
+        if (d_w != nullptr) dot = dot4(gv, rows[i * D4 + c], dot);
       }
     }
     if (d_w != nullptr) {
-      for (int m = W >> 1; m > 0; m >>= 1) dot += __shfl_xor(dot, m, W);
+      dot = group_sum(dot, W);
       if (lane == 0) d_w[i] = dot;
     }
   }
@@ -356,25 +398,30 @@ __global__ __launch_bounds__(kBagNT) void bag_max_backward_kernel(const float4* 
 
 // ---- pooling through a map (the dedup route: include/ttemb_unique.h) ---------------------------------------
 // The rows buffer holds one row per DISTINCT id ([cap][D]); position n of the id list reads rows[map[n]].  The forward is
-// bag_partial_kernel / bag_reduce_kernel with that indirection (kernels of their own: the ones above are not touched) and the
-// same summation orders, so for equal row bits it gives their bits on the expanded rows.  WEIGHTED = false is a weight of 1
-// without the loads: 1 * r and fma(1, r, a) round as r and r + a.  The five kernels take the device id count of the *_n
-// convention above (include/ttemb_unique_n.h): every one uses c = live_count(nnz, nnz_dev) where it would use nnz.
+// chunk_partials / segment_sums over the same bags with that indirection in the terms, so for equal row bits it gives the
+// plain pool's bits on the expanded rows.  WEIGHTED = false is a weight of 1 without the loads: 1 * r and fma(1, r, a) round
+// as r and r + a.  The five kernels take the device id count of the *_n convention above (include/ttemb_unique_n.h): every
+// one uses c = live_count(nnz, nnz_dev) where it would use nnz.
 __device__ __forceinline__ int64_t clamp_row(int32_t m, int64_t cap) { return m < 0 ? 0 : (m >= cap ? cap - 1 : (int64_t)m); }
 
-// sum_{n in [a, e)} w[n] rows[map[n]][c], n in order (a < e): weighted_sum's order
+// terms w[n] rows[map[n]][c]
 template <bool WEIGHTED>
-__device__ __forceinline__ float4 mapped_sum(const float4* __restrict__ rows, int64_t cap, const int32_t* __restrict__ map,
-                                             const float* __restrict__ w, int64_t D4, int64_t c, int64_t a, int64_t e) {
-  float4 acc = rows[clamp_row(map[a], cap) * D4 + c];
-  if constexpr (WEIGHTED) acc = f4_scale(w[a], acc);
+struct MappedTerms {
+  const float4* __restrict__ rows;
+  int64_t cap;
+  const int32_t* __restrict__ map;
+  const float* __restrict__ w;
+  __device__ __forceinline__ float4 sum(int64_t D4, int64_t c, int64_t a, int64_t e) const {
+    float4 acc = rows[clamp_row(map[a], cap) * D4 + c];
+    if constexpr (WEIGHTED) acc = f4_scale(w[a], acc);
 #pragma unroll 8
-  for (int64_t n = a + 1; n < e; ++n) {
-    const float4 r = rows[clamp_row(map[n], cap) * D4 + c];
-    if constexpr (WEIGHTED) acc = f4_fma(w[n], r, acc); else acc = f4_add(r, acc);
+    for (int64_t n = a + 1; n < e; ++n) {
+      const float4 r = rows[clamp_row(map[n], cap) * D4 + c];
+      if constexpr (WEIGHTED) acc = f4_fma(w[n], r, acc); else acc = f4_add(r, acc);
+    }
+    return acc;
   }
-  return acc;
-}
+};
 
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kBagNT) void bag_partial_mapped_kernel(const float4* __restrict__ rows, int64_t cap,
@@ -382,25 +429,7 @@ __global__ __launch_bounds__(kBagNT) void bag_partial_mapped_kernel(const float4
                                                                     const int64_t* __restrict__ offsets, int64_t nnz,
                                                                     const int32_t* __restrict__ nnz_dev, int64_t B,
                                                                     int64_t D4, int shift, float4* __restrict__ partial) {
-  nnz = live_count(nnz, nnz_dev);
-  const int64_t nchunks = chunks_of(nnz);
-  const int W = 1 << shift;
-  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
-  const int64_t per_block = kBagNT >> shift;
-  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
-    const int64_t s = k * kBagChunk, e = s + kBagChunk < nnz ? s + kBagChunk : nnz;
-    const int64_t bs = bag_of_position(offsets, B, s), be = bag_of_position(offsets, B, e - 1);
-    for (int which = 0; which < 2; ++which) {
-      const int64_t b = which == 0 ? bs : be;
-      if (which == 1 && be == bs) break;
-      int64_t n0, n1;
-      bag_range(offsets, nnz, b, n0, n1);
-      const int64_t a = n0 > s ? n0 : s, z = n1 < e ? n1 : e;
-      if (n1 - n0 <= kBagChunk || a >= z) continue;
-      float4* dst = partial + (2 * k + (n0 < s ? 0 : 1)) * D4;
-      for (int64_t c = lane; c < D4; c += W) dst[c] = mapped_sum<WEIGHTED>(rows, cap, map, w, D4, c, a, z);
-    }
-  }
+  chunk_partials(BagSegs{offsets, B, live_count(nnz, nnz_dev)}, MappedTerms<WEIGHTED>{rows, cap, map, w}, D4, shift, partial);
 }
 
 template <bool WEIGHTED>
@@ -410,28 +439,7 @@ __global__ __launch_bounds__(kBagNT) void bag_reduce_mapped_kernel(const float4*
                                                                    const int32_t* __restrict__ nnz_dev, int64_t B,
                                                                    int64_t D4, int shift, const float4* __restrict__ partial,
                                                                    float4* __restrict__ out) {
-  nnz = live_count(nnz, nnz_dev);
-  const int W = 1 << shift;
-  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
-  const int64_t per_block = kBagNT >> shift;
-  for (int64_t b = (int64_t)blockIdx.x * per_block + g; b < B; b += (int64_t)gridDim.x * per_block) {
-    int64_t n0, n1;
-    bag_range(offsets, nnz, b, n0, n1);
-    float4* dst = out + b * D4;
-    if (n1 - n0 > kBagChunk) {
-      const int64_t k0 = n0 / kBagChunk, k1 = (n1 - 1) / kBagChunk;
-      for (int64_t c = lane; c < D4; c += W) {
-        float4 acc = partial[(2 * k0 + 1) * D4 + c];
-#pragma unroll 8
-        for (int64_t k = k0 + 1; k <= k1; ++k) acc = f4_add(acc, partial[2 * k * D4 + c]);
-        dst[c] = acc;
-      }
-    } else if (n1 > n0) {
-      for (int64_t c = lane; c < D4; c += W) dst[c] = mapped_sum<WEIGHTED>(rows, cap, map, w, D4, c, n0, n1);
-    } else {
-      for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-  }
+  segment_sums(BagSegs{offsets, B, live_count(nnz, nnz_dev)}, MappedTerms<WEIGHTED>{rows, cap, map, w}, D4, shift, partial, out);
 }
 
 // The backward sums, per distinct id j < U, the gradients of its positions: the sorted position list perm (positions by id,
@@ -439,22 +447,25 @@ __global__ __launch_bounds__(kBagNT) void bag_reduce_mapped_kernel(const float4*
 // [seg[j], seg[j + 1]) and its term k is w[perm[k]] dOut[bag(perm[k])], zero for a position outside every bag.
 __device__ __forceinline__ int64_t clamp_to(int64_t p, int64_t hi) { return p < 0 ? 0 : (p > hi ? hi : p); }
 
-// [s0, s1) of segment j, clamped to the sorted list like bag_range
-__device__ __forceinline__ void seg_range(const int64_t* __restrict__ seg, int64_t nnz, int64_t j, int64_t& s0, int64_t& s1) {
-  s0 = clamp_to(seg[j], nnz);
-  s1 = clamp_to(seg[j + 1], nnz);
-  s1 = s1 < s0 ? s0 : s1;
-}
-
-// the segment of sorted position k: the last j < U with seg[j] <= k (seg[0] = 0 <= k)
-__device__ __forceinline__ int64_t seg_of_position(const int64_t* __restrict__ seg, int64_t U, int64_t k) {
-  int64_t lo = 0, hi = U;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (seg[mid] <= k) lo = mid; else hi = mid;
+struct SortedSegs {
+  const int64_t* __restrict__ seg;
+  int64_t count, end;   // U and seg[U], the end of the sorted list
+  // the segment of sorted position k: the last j < U with seg[j] <= k (seg[0] = 0 <= k)
+  __device__ __forceinline__ int64_t of(int64_t k) const {
+    int64_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (seg[mid] <= k) lo = mid; else hi = mid;
+    }
+    return lo;
   }
-  return lo;
-}
+  // [s0, s1) of segment j, clamped to the sorted list like bag_range
+  __device__ __forceinline__ void range(int64_t j, int64_t& s0, int64_t& s1) const {
+    s0 = clamp_to(seg[j], end);
+    s1 = clamp_to(seg[j + 1], end);
+    s1 = s1 < s0 ? s0 : s1;
+  }
+};
 
 // bagidx[n] = the bag of position n, -1 outside every bag: one thread per position, so the binary searches of bag_of_position
 // run side by side ONCE per call instead of one after the other inside every segment sum (the sums then read one word per
@@ -466,36 +477,37 @@ __global__ __launch_bounds__(kBagNT) void position_bags_kernel(const int64_t* __
     bagidx[n] = n >= first && n < last ? (int32_t)bag_of_position(offsets, B, n) : -1;
 }
 
-// term k of the sorted list, column c: the gradient row of its position's bag (zeros outside every bag) and, WEIGHTED, its weight
+// terms w[perm[k]] dOut[bag(perm[k])][c] of the sorted list
 template <bool WEIGHTED>
-__device__ __forceinline__ float4 mapped_term(const float4* __restrict__ d_out, const float* __restrict__ w,
-                                              const int32_t* __restrict__ perm, const int32_t* __restrict__ bagidx, int64_t nnz,
-                                              int64_t D4, int64_t c, int64_t k, float& wk) {
-  const int64_t p = clamp_to(perm[k], nnz - 1);
-  if constexpr (WEIGHTED) wk = w[p];
-  const int64_t b = bagidx[p];   // (< B: position_bags_kernel wrote it in this call)
-  if (b >= 0) return d_out[b * D4 + c];
-  return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-}
-
-// sum of the terms [a, e) in k order (a < e): weighted_sum's rule -- the first term a product, then one fma per term
-template <bool WEIGHTED>
-__device__ __forceinline__ float4 mapped_term_sum(const float4* __restrict__ d_out, const float* __restrict__ w,
-                                                  const int32_t* __restrict__ perm, const int32_t* __restrict__ bagidx,
-                                                  int64_t nnz, int64_t D4, int64_t c, int64_t a, int64_t e) {
-  float wk = 1.0f;
-  float4 acc = mapped_term<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, a, wk);
-  if constexpr (WEIGHTED) acc = f4_scale(wk, acc);
-#pragma unroll 4
-  for (int64_t k = a + 1; k < e; ++k) {
-    const float4 gv = mapped_term<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, k, wk);
-    if constexpr (WEIGHTED) acc = f4_fma(wk, gv, acc); else acc = f4_add(gv, acc);
+struct GradTerms {
+  const float4* __restrict__ d_out;
+  const float* __restrict__ w;
+  const int32_t* __restrict__ perm;
+  const int32_t* __restrict__ bagidx;
+  int64_t nnz;   // the live id count
+  // term k, column c: the gradient row of its position's bag (zeros outside every bag) and, WEIGHTED, its weight
+  __device__ __forceinline__ float4 term(int64_t D4, int64_t c, int64_t k, float& wk) const {
+    const int64_t p = clamp_to(perm[k], nnz - 1);
+    if constexpr (WEIGHTED) wk = w[p];
+    const int64_t b = bagidx[p];   // (< B: position_bags_kernel wrote it in this call)
+    if (b >= 0) return d_out[b * D4 + c];
+    return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-  return acc;
-}
+  __device__ __forceinline__ float4 sum(int64_t D4, int64_t c, int64_t a, int64_t e) const {
+    float wk = 1.0f;
+    float4 acc = term(D4, c, a, wk);
+    if constexpr (WEIGHTED) acc = f4_scale(wk, acc);
+#pragma unroll 4
+    for (int64_t k = a + 1; k < e; ++k) {
+      const float4 gv = term(D4, c, k, wk);
+      if constexpr (WEIGHTED) acc = f4_fma(wk, gv, acc); else acc = f4_add(gv, acc);
+    }
+    return acc;
+  }
+};
 
-// bag_partial_kernel on the sorted list: the part of every LONG segment (more than kBagChunk positions) that lies in chunk k
-// goes to one of the chunk's two slots.  Chunks at or past seg[U] = the end of the list do not exist.
+// d_rows[j], j < U: the chunk partials of the long segments (chunks at or past seg[U] = the end of the list do not exist),
+// then every segment.  One lane group per distinct id; the launches are sized by nnz, the loops stop at seg[U] and U.
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kBagNT) void seg_partial_mapped_kernel(const float4* __restrict__ d_out, const float* __restrict__ w,
                                                                     const int32_t* __restrict__ perm,
@@ -505,32 +517,11 @@ __global__ __launch_bounds__(kBagNT) void seg_partial_mapped_kernel(const float4
                                                                     const int32_t* __restrict__ nnz_dev, int64_t cap,
                                                                     int64_t D4, int shift, float4* __restrict__ partial) {
   nnz = live_count(nnz, nnz_dev);
-  const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
+  const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);   // the distinct ids of the live part
   if (U <= 0) return;
-  const int64_t end = clamp_to(seg[U], nnz);
-  const int64_t nchunks = chunks_of(end);
-  const int W = 1 << shift;
-  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
-  const int64_t per_block = kBagNT >> shift;
-  for (int64_t k = (int64_t)blockIdx.x * per_block + g; k < nchunks; k += (int64_t)gridDim.x * per_block) {
-    const int64_t s = k * kBagChunk, e = s + kBagChunk < end ? s + kBagChunk : end;
-    const int64_t js = seg_of_position(seg, U, s), je = seg_of_position(seg, U, e - 1);
-    for (int which = 0; which < 2; ++which) {
-      const int64_t j = which == 0 ? js : je;
-      if (which == 1 && je == js) break;
-      int64_t s0, s1;
-      seg_range(seg, end, j, s0, s1);
-      const int64_t a = s0 > s ? s0 : s, z = s1 < e ? s1 : e;
-      if (s1 - s0 <= kBagChunk || a >= z) continue;
-      float4* dst = partial + (2 * k + (s0 < s ? 0 : 1)) * D4;
-      for (int64_t c = lane; c < D4; c += W)
-        dst[c] = mapped_term_sum<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, a, z);
-    }
-  }
+  chunk_partials(SortedSegs{seg, U, clamp_to(seg[U], nnz)}, GradTerms<WEIGHTED>{d_out, w, perm, bagidx, nnz}, D4, shift, partial);
 }
 
-// d_rows[j], j < U: a short segment one sum in k order, a long one the sum of its chunk partials in chunk order.  One lane
-// group per distinct id; the launch is sized by nnz, the loop stops at U.
 template <bool WEIGHTED>
 __global__ __launch_bounds__(kBagNT) void seg_reduce_mapped_kernel(const float4* __restrict__ d_out, const float* __restrict__ w,
                                                                    const int32_t* __restrict__ perm,
@@ -543,29 +534,7 @@ __global__ __launch_bounds__(kBagNT) void seg_reduce_mapped_kernel(const float4*
   nnz = live_count(nnz, nnz_dev);
   const int64_t U = live_count(nnz < cap ? nnz : cap, count_dev);
   if (U <= 0) return;
-  const int64_t end = clamp_to(seg[U], nnz);
-  const int W = 1 << shift;
-  const int g = threadIdx.x >> shift, lane = threadIdx.x & (W - 1);
-  const int64_t per_block = kBagNT >> shift;
-  for (int64_t j = (int64_t)blockIdx.x * per_block + g; j < U; j += (int64_t)gridDim.x * per_block) {
-    int64_t s0, s1;
-    seg_range(seg, end, j, s0, s1);
-    float4* dst = d_rows + j * D4;
-    if (s1 - s0 > kBagChunk) {
-      const int64_t k0 = s0 / kBagChunk, k1 = (s1 - 1) / kBagChunk;
-      for (int64_t c = lane; c < D4; c += W) {
-        float4 acc = partial[(2 * k0 + 1) * D4 + c];
-#pragma unroll 8
-        for (int64_t k = k0 + 1; k <= k1; ++k) acc = f4_add(acc, partial[2 * k * D4 + c]);
-        dst[c] = acc;
-      }
-    } else if (s1 > s0) {
-      for (int64_t c = lane; c < D4; c += W)
-        dst[c] = mapped_term_sum<WEIGHTED>(d_out, w, perm, bagidx, nnz, D4, c, s0, s1);
-    } else {
-      for (int64_t c = lane; c < D4; c += W) dst[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-  }
+  segment_sums(SortedSegs{seg, U, clamp_to(seg[U], nnz)}, GradTerms<WEIGHTED>{d_out, w, perm, bagidx, nnz}, D4, shift, partial, d_rows);
 }
 
 // d_w[n] = <dOut[bag(n)], rows[map[n]]>, 0 outside every bag: the dot product and lane butterfly of
@@ -587,16 +556,9 @@ __global__ __launch_bounds__(kBagNT) void mapped_weight_grad_kernel(const float4
     float dot = 0.0f;
     for (int64_t k = 0; k < passes; ++k) {   // the same trip count on every lane of the group (the butterfly needs them all)
       const int64_t c = lane + (k << shift);
-      if (c < D4 && in_bag) {
-        const float4 gv = d_out[b * D4 + c];
-        const float4 r = rows[m * D4 + c];
-        dot = fmaf(gv.x, r.x, dot);
-        dot = fmaf(gv.y, r.y, dot);
-        dot = fmaf(gv.z, r.z, dot);
-        dot = fmaf(gv.w, r.w, dot);
-      }
+      if (c < D4 && in_bag) dot = dot4(d_out[b * D4 + c], rows[m * D4 + c], dot);
     }
-    for (int s = W >> 1; s > 0; s >>= 1) dot += __shfl_xor(dot, s, W);
+    dot = group_sum(dot, W);
     if (lane == 0) d_w[i] = dot;
   }
 }
@@ -625,32 +587,53 @@ int64_t ttemb_bag_workspace_bytes(int64_t nnz, int64_t B, int64_t D) {
   return kBagHeader + 2 * chunks_of(nnz) * D * (int64_t)sizeof(float);
 }
 
-int ttemb_bag_reduce_n(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
-                       int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes, void* stream) {
-  int rc = check_sizes("ttemb_bag_reduce", nnz, B, D);
+// ttemb_bag_reduce_n (`what`, mapped = false: one row per position, weights required) and ttemb_bag_reduce_mapped_n (mapped:
+// rows[map[n]] of `cap` rows, weights may be null, nnz has to fit the int32 map): the same two launches over the same chunks
+static int reduce_call(const char* what, bool mapped, const float* rows, int64_t cap, const int32_t* map, const float* weights,
+                       const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev, int64_t B, int64_t D, float* output,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+  int rc = check_sizes(what, nnz, B, D);
   if (rc) return rc;
+  if (mapped && nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "%s: nnz = %lld does not fit the int32 map", what, (long long)nnz);
   if (B == 0) return TTEMB_OK;
-  if (offsets == nullptr || output == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: offsets / output is null");
-  if (nnz > 0 && (rows == nullptr || weights == nullptr))
-    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: rows / weights is null");
-  if (misaligned(rows) || misaligned(output)) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce: rows / output not 16-byte aligned");
+  if (offsets == nullptr || output == nullptr) return fail(TTEMB_E_BADARG, "%s: offsets / output is null", what);
+  if (nnz > 0 && mapped && (rows == nullptr || map == nullptr || cap < 1))
+    return fail(TTEMB_E_BADARG, "%s: rows / map is null or cap < 1", what);
+  if (nnz > 0 && !mapped && (rows == nullptr || weights == nullptr)) return fail(TTEMB_E_BADARG, "%s: rows / weights is null", what);
+  if (misaligned(rows) || misaligned(output)) return fail(TTEMB_E_BADARG, "%s: rows / output not 16-byte aligned", what);
   const int64_t need = ttemb_bag_workspace_bytes(nnz, B, D);
   if (workspace_bytes < need || workspace == nullptr)
-    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_reduce: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
-                (long long)need);
+    return fail(TTEMB_E_WORKSPACE, "%s: workspace of %lld bytes, need %lld", what, (long long)workspace_bytes, (long long)need);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int64_t D4 = D / 4, nch = chunks_of(nnz);
   const Groups gr = groups_of(D4);
   float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
   const float4* r4 = reinterpret_cast<const float4*>(rows);
-  if (nch > 0) {
-    hipLaunchKernelGGL(bag_partial_kernel, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, nnz_dev, B,
-                       D4, gr.shift, partial);
-    if ((rc = check_hip(hipGetLastError(), "bag_partial_kernel"))) return rc;
+  float4* o4 = reinterpret_cast<float4*>(output);
+  const dim3 gp(grid_of(nch, gr)), gb(grid_of(B, gr)), nt(kBagNT);
+  if (!mapped) {
+    if (nch > 0) {
+      hipLaunchKernelGGL(bag_partial_kernel, gp, nt, 0, st, r4, weights, offsets, nnz, nnz_dev, B, D4, gr.shift, partial);
+      if ((rc = check_hip(hipGetLastError(), "bag_partial_kernel"))) return rc;
+    }
+    hipLaunchKernelGGL(bag_reduce_kernel, gb, nt, 0, st, r4, weights, offsets, nnz, nnz_dev, B, D4, gr.shift, partial, o4);
+    return check_hip(hipGetLastError(), "bag_reduce_kernel");
   }
-  hipLaunchKernelGGL(bag_reduce_kernel, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, weights, offsets, nnz, nnz_dev, B, D4,
-                     gr.shift, partial, reinterpret_cast<float4*>(output));
-  return check_hip(hipGetLastError(), "bag_reduce_kernel");
+  const bool weighted = weights != nullptr;
+  if (nch > 0) {
+    hipLaunchKernelGGL((weighted ? bag_partial_mapped_kernel<true> : bag_partial_mapped_kernel<false>), gp, nt, 0, st, r4, cap, map,
+                       weights, offsets, nnz, nnz_dev, B, D4, gr.shift, partial);
+    if ((rc = check_hip(hipGetLastError(), "bag_partial_mapped_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL((weighted ? bag_reduce_mapped_kernel<true> : bag_reduce_mapped_kernel<false>), gb, nt, 0, st, r4, cap, map,
+                     weights, offsets, nnz, nnz_dev, B, D4, gr.shift, partial, o4);
+  return check_hip(hipGetLastError(), "bag_reduce_mapped_kernel");
+}
+
+int ttemb_bag_reduce_n(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, const int32_t* nnz_dev,
+                       int64_t B, int64_t D, float* output, void* workspace, int64_t workspace_bytes, void* stream) {
+  return reduce_call("ttemb_bag_reduce", false, rows, 0, nullptr, weights, offsets, nnz, nnz_dev, B, D, output, workspace,
+                     workspace_bytes, stream);
 }
 
 int ttemb_bag_reduce(const float* rows, const float* weights, const int64_t* offsets, int64_t nnz, int64_t B, int64_t D,
@@ -790,42 +773,8 @@ int ttemb_pad_weights(const int64_t* indices, const int64_t* offsets, const floa
 int ttemb_bag_reduce_mapped_n(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
                               int64_t nnz, const int32_t* nnz_dev, int64_t B, int64_t D, float* output, void* workspace,
                               int64_t workspace_bytes, void* stream) {
-  int rc = check_sizes("ttemb_bag_reduce_mapped", nnz, B, D);
-  if (rc) return rc;
-  if (nnz > kBagMaxIds) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: nnz = %lld does not fit the int32 map", (long long)nnz);
-  if (B == 0) return TTEMB_OK;
-  if (offsets == nullptr || output == nullptr) return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: offsets / output is null");
-  if (nnz > 0 && (rows == nullptr || map == nullptr || cap < 1))
-    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: rows / map is null or cap < 1");
-  if (misaligned(rows) || misaligned(output))
-    return fail(TTEMB_E_BADARG, "ttemb_bag_reduce_mapped: rows / output not 16-byte aligned");
-  const int64_t need = ttemb_bag_workspace_bytes(nnz, B, D);
-  if (workspace_bytes < need || workspace == nullptr)
-    return fail(TTEMB_E_WORKSPACE, "ttemb_bag_reduce_mapped: workspace of %lld bytes, need %lld", (long long)workspace_bytes,
-                (long long)need);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int64_t D4 = D / 4, nch = chunks_of(nnz);
-  const Groups gr = groups_of(D4);
-  float4* partial = reinterpret_cast<float4*>(reinterpret_cast<char*>(workspace) + kBagHeader);
-  const float4* r4 = reinterpret_cast<const float4*>(rows);
-  float4* o4 = reinterpret_cast<float4*>(output);
-  const bool weighted = weights != nullptr;
-  if (nch > 0) {
-    if (weighted)
-      hipLaunchKernelGGL(bag_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
-                         nnz, nnz_dev, B, D4, gr.shift, partial);
-    else
-      hipLaunchKernelGGL(bag_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets,
-                         nnz, nnz_dev, B, D4, gr.shift, partial);
-    if ((rc = check_hip(hipGetLastError(), "bag_partial_mapped_kernel"))) return rc;
-  }
-  if (weighted)
-    hipLaunchKernelGGL(bag_reduce_mapped_kernel<true>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
-                       nnz_dev, B, D4, gr.shift, partial, o4);
-  else
-    hipLaunchKernelGGL(bag_reduce_mapped_kernel<false>, dim3(grid_of(B, gr)), dim3(kBagNT), 0, st, r4, cap, map, weights, offsets, nnz,
-                       nnz_dev, B, D4, gr.shift, partial, o4);
-  return check_hip(hipGetLastError(), "bag_reduce_mapped_kernel");
+  return reduce_call("ttemb_bag_reduce_mapped", true, rows, cap, map, weights, offsets, nnz, nnz_dev, B, D, output, workspace,
+                     workspace_bytes, stream);
 }
 
 int ttemb_bag_reduce_mapped(const float* rows, int64_t cap, const int32_t* map, const float* weights, const int64_t* offsets,
@@ -869,19 +818,12 @@ int ttemb_bag_reduce_mapped_backward_n(const float* d_output, const float* weigh
   hipLaunchKernelGGL(position_bags_kernel, dim3(exact::ex_grid((nnz + kBagNT - 1) / kBagNT)), dim3(kBagNT), 0, st, offsets, nnz, B,
                      bagidx);
   if ((rc = check_hip(hipGetLastError(), "position_bags_kernel"))) return rc;
-  if (weights != nullptr) {
-    hipLaunchKernelGGL(seg_partial_mapped_kernel<true>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial);
-    if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
-    hipLaunchKernelGGL(seg_reduce_mapped_kernel<true>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial, dr4);
-  } else {
-    hipLaunchKernelGGL(seg_partial_mapped_kernel<false>, dim3(grid_of(nch, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial);
-    if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
-    hipLaunchKernelGGL(seg_reduce_mapped_kernel<false>, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4, weights, perm, seg,
-                       count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial, dr4);
-  }
+  const bool weighted = weights != nullptr;
+  hipLaunchKernelGGL((weighted ? seg_partial_mapped_kernel<true> : seg_partial_mapped_kernel<false>), dim3(grid_of(nch, gr)),
+                     dim3(kBagNT), 0, st, g4, weights, perm, seg, count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial);
+  if ((rc = check_hip(hipGetLastError(), "seg_partial_mapped_kernel"))) return rc;
+  hipLaunchKernelGGL((weighted ? seg_reduce_mapped_kernel<true> : seg_reduce_mapped_kernel<false>), dim3(grid_of(nnz, gr)),
+                     dim3(kBagNT), 0, st, g4, weights, perm, seg, count_dev, bagidx, nnz, nnz_dev, cap, D4, gr.shift, partial, dr4);
   if ((rc = check_hip(hipGetLastError(), "seg_reduce_mapped_kernel"))) return rc;
   if (d_weights != nullptr) {
     hipLaunchKernelGGL(mapped_weight_grad_kernel, dim3(grid_of(nnz, gr)), dim3(kBagNT), 0, st, g4,

@@ -216,7 +216,7 @@ __global__ void rowidx_kernel(const int64_t* __restrict__ offsets, int64_t B, in
 // kernel adds up the counts of the blocks before its own (a few hundred coalesced loads), ranks its ids with a
 // ballot, finds their bags and writes the three partitioned arrays.  (rowidx expansion + lookup + a rocPRIM scan
 // -- two launches -- + scatter were five launches and 36 us for 409 600 ids.)
-constexpr int kPartThreads = 256;
+constexpr int kPartThreads = kRankTile;   // (partition_rank, ttemb_common.h, ranks inside a workgroup of this size)
 
 // UPDATE: the LFU update of the same ids (ttemb_cache_update, the find-first form) rides in the probe pass -- the class
 // calls update_cache_state and preprocess_indices_sync back to back on the same ids (tt_embeddings_ops.py:836-870), and
@@ -252,49 +252,6 @@ __global__ __launch_bounds__(kPartThreads) void cache_lookup_kernel(const int64_
   if (n == 0 && dup_stamp != nullptr) nnz_tt[1] = 0;   // "no cache row met twice" until the scatter kernel finds one
   const int c = __syncthreads_count(n < nnz && where < 0);
   if (threadIdx.x == 0) blockcnt[blockIdx.x] = c;
-}
-
-// The rank core of the stable partitions (this one and ttemb_drop_padding's): the number of flagged positions before this
-// thread's, in the whole call -- the counts of the blocks before `block` (blockcnt, summed by wave 0: a few hundred
-// coalesced loads) plus a ballot rank inside the block.  No waits between workgroups.  `wave_cnt` / `wave_ball` / `before_lds`
-// are the caller's LDS (wave_ball may be null); `before_block` and `total` (flagged positions of this block) come back too.
-__device__ __forceinline__ int64_t partition_rank(const int32_t* __restrict__ blockcnt, int64_t block, bool f, int* wave_cnt,
-                                                  unsigned long long* wave_ball, int64_t* before_lds, int64_t& before_block,
-                                                  int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (wave == 0) {
-    int64_t v = 0;
-    for (int64_t b0 = 0; b0 < block; b0 += 8 * kWave) {   // eight loads per lane in flight, then the sums
-      int32_t c[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t b = b0 + k * kWave + lane;
-        c[k] = b < block ? blockcnt[b] : 0;
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v += c[k];
-    }
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-      const uint32_t lo_w = __shfl_down((uint32_t)v, d, kWave), hi_w = __shfl_down((uint32_t)((uint64_t)v >> 32), d, kWave);
-      v += (int64_t)((uint64_t)lo_w | ((uint64_t)hi_w << 32));
-    }
-    if (lane == 0) *before_lds = v;
-  }
-  const unsigned long long ball = __ballot(f);
-  if (lane == 0) {
-    wave_cnt[wave] = __popcll(ball);
-    if (wave_ball != nullptr) wave_ball[wave] = ball;
-  }
-  __syncthreads();
-  before_block = *before_lds;
-  int64_t before = before_block + __popcll(ball & ((1ull << lane) - 1ull));
-  total = 0;
-  for (int w = 0; w < kPartThreads / kWave; ++w) {
-    if (w < wave) before += wave_cnt[w];
-    total += wave_cnt[w];
-  }
-  return before;
 }
 
 // selected (TT) items keep input order at the front; rejected (cached) items fill the

@@ -264,6 +264,51 @@ __device__ __forceinline__ int64_t live_count(int64_t nnz, const int32_t* nnz_de
   return c < nnz ? (c < 0 ? 0 : c) : nnz;
 }
 
+// The rank core of the stable partitions (the cache's, ttemb_drop_padding's) and of the distinct-id pass (ttemb_unique.hip):
+// the number of flagged positions before this thread's, in the whole call -- the counts of the tiles before `block` (blockcnt,
+// summed by wave 0: a few hundred coalesced loads) plus a ballot rank inside the tile.  A tile is one workgroup of kRankTile
+// threads.  No waits between workgroups.  `wave_cnt` / `wave_ball` / `before_lds` are the caller's LDS (wave_ball may be
+// null); `before_block` and `total` (flagged positions of this tile) come back too.
+constexpr int kRankTile = 256;
+__device__ __forceinline__ int64_t partition_rank(const int32_t* __restrict__ blockcnt, int64_t block, bool f, int* wave_cnt,
+                                                  unsigned long long* wave_ball, int64_t* before_lds, int64_t& before_block,
+                                                  int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (wave == 0) {
+    int64_t v = 0;
+    for (int64_t b0 = 0; b0 < block; b0 += 8 * kWave) {   // eight loads per lane in flight, then the sums
+      int32_t c[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int64_t b = b0 + k * kWave + lane;
+        c[k] = b < block ? blockcnt[b] : 0;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v += c[k];
+    }
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+      const uint32_t lo_w = __shfl_down((uint32_t)v, d, kWave), hi_w = __shfl_down((uint32_t)((uint64_t)v >> 32), d, kWave);
+      v += (int64_t)((uint64_t)lo_w | ((uint64_t)hi_w << 32));
+    }
+    if (lane == 0) *before_lds = v;
+  }
+  const unsigned long long ball = __ballot(f);
+  if (lane == 0) {
+    wave_cnt[wave] = __popcll(ball);
+    if (wave_ball != nullptr) wave_ball[wave] = ball;
+  }
+  __syncthreads();
+  before_block = *before_lds;
+  int64_t before = before_block + __popcll(ball & ((1ull << lane) - 1ull));
+  total = 0;
+  for (int w = 0; w < kRankTile / kWave; ++w) {
+    if (w < wave) before += wave_cnt[w];
+    total += wave_cnt[w];
+  }
+  return before;
+}
+
 // id -> per-core row numbers (reference: FBTT/tt_embeddings_cuda.cu:796-802).
 __device__ __forceinline__ void split_index(const DevShape& s, int64_t idx, int (&i)[TTEMB_MAX_CORES]) {
   // an id outside the table is clamped as a whole (to the first / last row), the rule of every kernel family, so a bad
